@@ -70,6 +70,13 @@ from inside this process); `cpu_baseline` times the numpy/cKDTree oracle (oracle
 reference's CPU path — the reference itself does not exist on the GPU box) on the same workload: median of 10 frames
 after two warm-up frames (~26 s of CPU work), the kd-tree build timed separately.  The reference's own
 `ICPFrameToModel` timed through the shims in the build container is kept as context in profiles/ (tools/time_reference.py).
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it sets up, warms up,
+times the K steps without instrumentation and prints the line (`value`, `ms_per_step`, the per-step spread, the pose
+error against ground truth).  The legs above, the HIP-event roofline timing and `cpu_baseline` run with `--full`, where
+the switches that select among them apply as they always did.  `--dump-outputs DIR` writes what the last timed step
+computed as .npy files (the inputs are seeded: the same arguments give the same inputs), so that two builds can be
+compared output for output.
 """
 import argparse
 import contextlib
@@ -162,6 +169,14 @@ def parse():
                     help="N > 1, replicas mode: 1 = also run the `sharded` and `c4` legs behind the headline; 0: skip")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event timing of the search kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything next to the headline: the HIP-event roofline timing, headline_60, "
+                         "reference_schedule, loop, throughput, throughput_batched, plugin, odometry_loop, the multi-GPU "
+                         "legs and cpu_baseline (the switches above select among them).  Without it a run sets up, warms "
+                         "up, times --steps steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's sequence) as "
+                         "DIR/<name>.npy: the registration result, the scan's vertex map and the re-expressed local map")
     return ap.parse_args()
 
 
@@ -914,6 +929,25 @@ def timed_region(extra, main_tr, steps, dist, dev):
     return res, elapsed
 
 
+def dump_outputs(directory, tr, res):
+    """What the last timed step computed, as float32 / float64 .npy files (a few MB): the registration result the
+    caller receives, the vertex map of the step's projection and the local map after the step's update (rows sorted, so
+    that the file does not depend on the order the map is stored in)."""
+    os.makedirs(directory, exist_ok=True)
+    pts = tr.ctx.map_points()
+    arrays = {
+        "pose": np.asarray(res.pose, np.float32),
+        "params": np.asarray(res.params, np.float32),
+        "losses": np.asarray(res.losses, np.float64),
+        "dx": np.asarray(res.dx, np.float32),
+        "result_counts": np.array([res.iterations, res.converged, res.num_targets, res.normals_computed], np.float64),
+        "vertex_map": tr.vmap.detach().cpu().numpy().astype(np.float32),
+        "local_map": pts[np.lexsort((pts[:, 2], pts[:, 1], pts[:, 0]))].astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` without a launcher: re-execute this script under torch.distributed.run with N ranks on
     this node (127.0.0.1 rendezvous, a free port), pass the ranks' output through and return their exit code.  The ranks
@@ -1008,7 +1042,9 @@ def main():
     main_tr.run(args.warmup)
     for t_ in extra:
         t_.done.wait()
-    if not args.no_profile:
+    # the HIP-event timing of the dominant kernel feeds the roofline figure, a --full figure: a plain run times bare steps
+    profile = args.full and not args.no_profile
+    if profile:
         # HIP-event pairs around the dominant kernel inside the timed region — on every PROFILE_EVERY-th frame: an event
         # breaks the back-to-back dispatch of the kernels around it; a frame with its 20 iteration launches bracketed is
         # ~0.15 ms slower than an un-instrumented one (measured: 0.653 ms per step with --no-profile, 0.684 with every
@@ -1017,24 +1053,26 @@ def main():
         main_tr.ctx.set_option("profile_rotate", 1)
         main_tr.ctx.profile_enable(int(os.environ.get("BENCH_PROF_MASK", "1")))  # 1: iteration kernel; 4: + normals
     res, elapsed = timed_region(extra, main_tr, args.steps, dist, dev)
-    prof = main_tr.ctx.profile_read() if not args.no_profile else None
-    prof_iter = main_tr.ctx.profile_read_iterations(args.iters) if not args.no_profile else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main_tr, res)
+    prof = main_tr.ctx.profile_read() if profile else None
+    prof_iter = main_tr.ctx.profile_read_iterations(args.iters) if profile else None
     # a short run (the driver's 20 steps) sees every iteration index ONCE — one sample each, some of them on the two
     # turn-around frames of the trajectory: 100 more frames of the same loop with the same sampling (outside the timed
     # region; all ranks take part), reported next to the timed region's own figure as `avg_launch_us_long`
     prof_iter_long = None
-    if not args.no_profile and args.steps < MIN_STEPS_FOR_HEADLINE and not extra:
+    if profile and args.steps < MIN_STEPS_FOR_HEADLINE and not extra:
         main_tr.run(100)
         prof_iter_long = main_tr.ctx.profile_read_iterations(args.iters)
         del main_tr.step_ms[args.steps:]
     main_tr.ctx.profile_enable(0)
     main_tr.ctx.set_option("profile_rotate", 0)
-    event_floor_us = main_tr.ctx.profile_event_floor(200) if not args.no_profile else None
+    event_floor_us = main_tr.ctx.profile_event_floor(200) if profile else None
 
     # fewer than 50 timed steps (the driver's line has 20 = 13 ms): the same loop once more over 60 steps, so that the
     # figure does not rest on a 13 ms window (all ranks take part; instrumentation off)
     headline_60 = None
-    if args.steps < MIN_STEPS_FOR_HEADLINE and not extra:
+    if args.full and args.steps < MIN_STEPS_FOR_HEADLINE and not extra:
         _, e60 = timed_region([], main_tr, 60, dist, dev)
         scans60 = 60 * (1 if sharded else world)
         sm60 = sorted(main_tr.step_ms[-60:])
@@ -1045,7 +1083,7 @@ def main():
     # every map update (carry_normals=0), 40 steps after 5 untimed ones, outside the headline's timed region
     ref_sched = None
     carry_default = not any(o.replace(" ", "").startswith("carry_normals=") for o in args.option)
-    if carry_default and not extra and not args.no_cpu_baseline:
+    if args.full and carry_default and not extra and not args.no_cpu_baseline:
         main_tr.ctx.set_option("carry_normals", 0)
         main_tr.run(5)
         n0 = len(main_tr.step_ms)
@@ -1062,7 +1100,7 @@ def main():
 
     # the closed-circuit trajectory next to the headline (single sequence, rank 0 only, outside the headline timing)
     loop = None
-    if rank == 0 and args.loop_steps > 0 and args.trajectory != "loop" and not sharded and S == 1:
+    if args.full and rank == 0 and args.loop_steps > 0 and args.trajectory != "loop" and not sharded and S == 1:
         lt = Tracker(args, rank * S, "loop", 3 + args.loop_steps, local_rank)
         lt.run(3)
         torch.cuda.synchronize()
@@ -1081,7 +1119,7 @@ def main():
     # a process has four hardware queues, and a stream more than the sequences need makes two of them share one
     # (2470 instead of 3430 scans/s, measured)
     through = batched = None
-    if rank == 0 and world == 1 and S == 1 and not sharded and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and S == 1 and not sharded and not args.no_cpu_baseline:
         sizes = parse_batch_sizes(args.batched_leg)
         want = max([args.throughput_leg - 1 if args.throughput_leg > 1 else 0] + [b for b, _ in sizes])
         # the sequences of both throughput legs: generated by worker PROCESSES, one sequence each (see SequenceThread: threads
@@ -1097,7 +1135,7 @@ def main():
             except Exception as e:  # a failed leg must not cost the line its headline
                 batched = {"error": repr(e)}
     plugin = odo_loop = None
-    if rank == 0 and not sharded and S == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not sharded and S == 1 and not args.no_cpu_baseline:
         if args.plugin_steps > 0:
             try:
                 plugin = plugin_leg(args, main_tr, local_rank, args.plugin_steps, max(3, args.warmup))
@@ -1109,7 +1147,7 @@ def main():
             except Exception as e:
                 odo_loop = {"error": repr(e)}
     multi = None
-    if world > 1 and not sharded and S == 1 and args.multi_gpu_legs:
+    if args.full and world > 1 and not sharded and S == 1 and args.multi_gpu_legs:
         multi = {"sharded": sharded_legs(args, dist, rank, world, local_rank, dev, steps=max(10, min(args.steps, 30)))}
         try:
             multi["c4"] = c4_leg(args, dist, rank, world, local_rank, dev, steps=4, warmup=2)
@@ -1228,7 +1266,7 @@ def main():
         if world > 1:
             out["rccl_ranks"] = world if dist.get_backend() == "nccl" else 0
             out["dist_backend"] = dist.get_backend()
-        if not args.no_cpu_baseline and world == 1 and os.environ.get("BENCH_DEV_SKIP_CPU_TIMING") != "1":  # (dev repro runs)
+        if args.full and not args.no_cpu_baseline and world == 1 and os.environ.get("BENCH_DEV_SKIP_CPU_TIMING") != "1":  # (dev repro runs)
             out["cpu_baseline"] = cpu_baseline(main_tr, args)
         print(json.dumps(out))
     for t_ in extra:

@@ -314,7 +314,7 @@ def test_bench_gpus_2_launches_its_own_ranks(torch_cuda):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3",
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -7,7 +7,7 @@ oracle/shims — is given the `*_mi355x` registry members of `register_with_refe
 replaced by the numpy `OracleContext` (no MI355X in this container; on the GPU box the reference is absent).  The
 resulting trajectory is compared with the reference's own `icp_F2M` run through the very same loop.
 
-Skipped where the reference checkout is absent.
+The two tests that import the reference are skipped where its checkout is absent.
 """
 import logging
 import os
@@ -20,7 +20,7 @@ import torch
 REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "slam")), reason="reference checkout not present")
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "slam")), reason="reference checkout not present")
 
 H, W, FRAMES = 16, 256, 4
 
@@ -95,6 +95,7 @@ def _reference_odometry():
             "alignment": {"mode": "point_to_plane_gauss_newton", "gauss_newton_config": GN}}
 
 
+@needs_reference
 def test_reference_slam_loop_drives_the_mi355x_odometry(reference):
     """ODOMETRY member `icp_F2M_mi355x` + DATASET member `synthetic_mi355x` + FILTER member `grid_sample_mi355x` under
     the reference's SLAM loop, DataLoader, collate function and pinned memory; same trajectory as the reference's own
@@ -119,6 +120,7 @@ def test_reference_slam_loop_drives_the_mi355x_odometry(reference):
     np.testing.assert_allclose(slam.initialization.initial_estimate, poses[-1], atol=1e-6)
 
 
+@needs_reference
 def test_reference_icp_runs_on_the_mi355x_inner_seams(reference):
     """The reference's OWN `ICPFrameToModel` with LOCAL_MAP member `hashgrid_local_map_mi355x` and RIGID_ALIGNMENT
     member `point_to_plane_gauss_newton_mi355x`: its loop multiplies the returned pose with its own tensor and sums the
@@ -139,10 +141,14 @@ def test_reference_icp_runs_on_the_mi355x_inner_seams(reference):
     assert isinstance(last, torch.Tensor) and last.ndim == 2 and last.shape[1] == 3
 
 
-def test_seams_refuse_what_they_do_not_implement(reference):
+def test_seams_refuse_what_they_do_not_implement(monkeypatch):
+    """Our classes alone (no reference code): the numpy `OracleContext` stands in for the GPU context."""
     from oracle_context import OracleContext
+    from pylidar_slam_amd import odometry as our_odometry
     from pylidar_slam_amd.odometry import (MI355XICPConfig, MI355XICPFrameToModel, PointToPlaneAlignment,
                                            SphericalProjector)
+    monkeypatch.setattr(our_odometry, "IcpContext", OracleContext)
+    monkeypatch.setattr(our_odometry, "_SHARED", {})
     with pytest.raises(AssertionError):  # more than one Gauss-Newton step per alignment is not silently ignored
         MI355XICPFrameToModel(MI355XICPConfig(alignment=dict(mode="point_to_plane_gauss_newton",
                                                              gauss_newton_config=dict(max_iters=3))),

@@ -7,7 +7,7 @@ cp $LIB /tmp/new_lib.so
 cd $R
 for r in 1 2 3 4 5; do for which in base new; do
 [ $which = base ] && cp $R/tools/ab/base_libicp_mi355x.so $LIB || cp /tmp/new_lib.so $LIB
-BENCH_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 20 --warmup 5 --multi-gpu-legs 1 > $OUT/two_$which.json 2> $OUT/two_$which.err
+BENCH_DIST_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 20 --warmup 5 --multi-gpu-legs 1 > $OUT/two_$which.json 2> $OUT/two_$which.err
 python - $OUT/two_$which.json $which <<'PY'
 import json,sys
 try:

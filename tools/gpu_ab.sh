@@ -11,7 +11,7 @@ if [ "${1:-}" = "--tests" ]; then
 fi
 for spec in "$@"; do
   name=${spec%%|*}; args=${spec#*|}
-  timeout 300 python bench.py --steps 60 --warmup 5 --no-cpu-baseline --loop-steps 0 $args > $OUT/ab_$name.json 2> $OUT/ab_$name.err
+  timeout 300 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --loop-steps 0 $args > $OUT/ab_$name.json 2> $OUT/ab_$name.err
   python - "$OUT/ab_$name.json" <<'PY'
 import json,sys
 try:

@@ -26,7 +26,7 @@ fi
 for r in $(seq 1 $ROUNDS); do
   for which in base new; do
     if [ $which = base ]; then cp $BASE $LIB; else cp /tmp/new_lib.so $LIB; fi
-    timeout 300 python bench.py --steps $STEPS --no-cpu-baseline --loop-steps 0 $EXTRA > $OUT/head_$which.json 2> $OUT/head_$which.err
+    timeout 300 python bench.py --full --steps $STEPS --no-cpu-baseline --loop-steps 0 $EXTRA > $OUT/head_$which.json 2> $OUT/head_$which.err
     python - $OUT/head_$which.json "$which" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d.get("roofline",{})

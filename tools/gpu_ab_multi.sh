@@ -9,7 +9,7 @@ cp $LIB /tmp/intree_lib.so
 cd $R
 for r in $(seq 1 $ROUNDS); do for n in $NAMES; do
   cp $R/tools/ab/${n}_libicp_mi355x.so $LIB
-  timeout 300 python bench.py --steps 70 --no-cpu-baseline --loop-steps 0 > $OUT/head_$n.json 2> $OUT/head_$n.err
+  timeout 300 python bench.py --full --steps 70 --no-cpu-baseline --loop-steps 0 > $OUT/head_$n.json 2> $OUT/head_$n.err
   timeout 900 python bench.py --leg throughput_batched --steps 100 --warmup 20 --batched-leg $BATCHED > $OUT/batched_$n.json 2> $OUT/batched_$n.err
   python - $OUT/head_$n.json $OUT/batched_$n.json "$n" <<'PY'
 import json,sys

@@ -5,9 +5,9 @@ TAG=${1:-final}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log; tail -3 $OUT/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-timeout 600 python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err; tail -c 400 $OUT/bench_line.json; echo
-timeout 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_line_20.json 2> $OUT/bench_line_20.err
-for s in 2 4; do timeout 300 python bench.py --sequences-per-gpu $s --no-cpu-baseline --loop-steps 0 > $OUT/bench_s$s.json 2> $OUT/bench_s$s.err; done
+timeout 600 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err; tail -c 400 $OUT/bench_line.json; echo
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line_20.json 2> $OUT/bench_line_20.err
+for s in 2 4; do timeout 300 python bench.py --full --sequences-per-gpu $s --no-cpu-baseline --loop-steps 0 > $OUT/bench_s$s.json 2> $OUT/bench_s$s.err; done
 for f in $OUT/bench_*.json; do python - "$f" <<'PY'
 import json,sys
 try:

@@ -9,7 +9,7 @@ HEAD_SHA=$(cat tools/.head_sha 2>/dev/null || echo unknown)
 R=$PWD
 timeout 1800 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log; tail -3 $OUT/pytest.log | cut -c1-200
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-LEGS_OFF="--no-cpu-baseline --loop-steps 0 --plugin-steps 0 --odometry-loop 0 --throughput-leg 0 --batched-leg="
+LEGS_OFF="--full --no-cpu-baseline --loop-steps 0 --plugin-steps 0 --odometry-loop 0 --throughput-leg 0 --batched-leg="
 CMD="python bench.py --steps 30 --warmup 5 $LEGS_OFF"
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o t -- python $R/bench.py --steps 30 --warmup 5 $LEGS_OFF > $R/$OUT/prof_bench.json 2> $R/$OUT/prof_bench.err )
 python tools/rocprof_iterate_summary.py $OUT/prof $OUT/rocprof_iterate_kernel.json $HEAD_SHA "rocprofv3 --kernel-trace --stats -- $CMD" > /dev/null
@@ -35,8 +35,8 @@ bash tools/batch_pmc.sh $TAG/batch8_pmc 8 > /dev/null 2>&1; head -24 $OUT/batch8
 cp $OUT/rocprof_iterate_kernel.json profiles/rocprof_iterate_kernel.json 2>/dev/null
 [ -s $OUT/pmc_search_kernel.json ] && cp $OUT/pmc_search_kernel.json profiles/pmc_search_kernel.json
 cp $OUT/rocprof_iterate_batch.json profiles/rocprof_iterate_batch.json 2>/dev/null
-T0=$(date +%s); timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_line_20.json 2> $OUT/bench_line_20.err; echo "bench20 rc=$? $(( $(date +%s) - T0 )) s"
-T0=$(date +%s); timeout 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err; echo "bench60 rc=$? $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line_20.json 2> $OUT/bench_line_20.err; echo "bench20 rc=$? $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); timeout 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err; echo "bench60 rc=$? $(( $(date +%s) - T0 )) s"
 for f in $OUT/bench_line_20.json $OUT/bench_line.json; do python - "$f" <<'PY'
 import json,sys
 try:
@@ -45,7 +45,7 @@ try:
 except Exception as e: print(sys.argv[1],"FAILED",e)
 PY
 done
-BENCH_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 > $OUT/bench_2ranks_gloo.json 2> $OUT/bench_2ranks_gloo.err; echo "2-rank rc=$?"
+BENCH_DIST_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --steps 20 --warmup 5 > $OUT/bench_2ranks_gloo.json 2> $OUT/bench_2ranks_gloo.err; echo "2-rank rc=$?"
 python - $OUT/bench_2ranks_gloo.json <<'PY'
 import json,sys
 try:
