@@ -472,6 +472,23 @@ int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
  *                              device-resident pose of the registration just launched (icp_odometry.py:379) — the B grid
  *                              rebuilds in four launches (held-back iterations are enqueued first: the update reads the END of
  *                              the registration);
+ *   icp_batch_map_update_staged  ICPFrameToModel.__update_map (slam/odometry/icp_odometry.py:360-380) for every member:
+ *                              insert[b] != 0: KdTreeLocalMap.update (slam/odometry/local_map.py:302-362) with the cloud member
+ *                              b staged by icp_map_stage_cloud — move the map by inv(rel), append the staged rows, evict the
+ *                              oldest cloud beyond local_map_size, rebuild, clear the normal cache (then the eager normals, as
+ *                              icp_map_update_staged); insert[b] == 0: the pose-only update (as icp_batch_map_update;
+ *                              "carry_normals" applies).  rel_poses = count x 16 floats, or NULL: every member's device-resident
+ *                              pose of its last registration.  inserted_out (optional, count entries): rows appended per
+ *                              member (0 for a pose-only member).  Per member the same map, window, normals and later
+ *                              registrations, bit for bit, as icp_map_update_staged(member, rel, ...) /
+ *                              icp_map_update(member, rel, NULL, ...) on that member alone.  The B grid builds take four or
+ *                              five launches, the neighbourhood lists ONE, the eager normals ONE per neighbourhood size (members
+ *                              whose normals another kernel computes — "knn_lanes" 2, "hoods" < 2, "normals_list" 1,
+ *                              "normals_tail_stream" 1, another num_neighbors_normals — get their own launch, as on their own).
+ *                              Every member is checked before any changes: ICP_ERR_INVALID_ARGUMENT, nothing changed, when a
+ *                              member is on another stream, an inserting member has no staged cloud, or rel_poses = NULL while a
+ *                              member never registered or an inserting member's registration has not been collected
+ *                              (icp_batch_register_end).  Held-back iterations are enqueued first;
  *   icp_batch_register_end     icp_register_end for every member (results[b]; loss_per_iter_out / dx_per_iter_out:
  *                              count x max_num_alignments (x 6) entries or NULL): ONE wait for all of them.  Returns the
  *                              first member's non-zero status, every member's own in results[b].status. */
@@ -485,6 +502,7 @@ int icp_batch_register_launch(icp_batch* batch, const float* const* xyz, const i
                               const float* init_poses, int from_last);
 int icp_batch_project(icp_batch* batch, const float* const* xyz, const int64_t* n, float* const* vmap_out);
 int icp_batch_map_update(icp_batch* batch);
+int icp_batch_map_update_staged(icp_batch* batch, const float* rel_poses, const int32_t* insert, int64_t* inserted_out);
 int icp_batch_register_end(icp_batch* batch, icp_register_result* results, double* loss_per_iter_out,
                            float* dx_per_iter_out);
 

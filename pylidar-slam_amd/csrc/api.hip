@@ -1993,7 +1993,8 @@ struct icp_batch {
     bool run_active = false, run_lead = false;
     int run_next = 0, run_iters = 0, run_done = 0;
     int run_prev_rows[ICP_BATCH_MAX_SEQUENCES] = {}, run_prev_quad[ICP_BATCH_MAX_SEQUENCES] = {};
-    // ... and of the batched grid build behind a map update: [count] GridBuildDesc per slot
+    // ... and of the batched grid build behind a map update: [count] GridBuildDesc per slot (then, for
+    // icp_batch_map_update_staged, ICP_BATCH_MAX_SEQUENCES NormalsBatchDesc: the eager normals of the same update)
     GridBuildDesc* grid_host[SLOTS] = {nullptr, nullptr, nullptr};
     DeviceBuffer grid_dev[SLOTS];
     hipEvent_t grid_copied[SLOTS] = {nullptr, nullptr, nullptr};
@@ -2257,6 +2258,24 @@ int icp_batch_project(icp_batch* b, const float* const* xyz, const int64_t* n, f
     return ICP_OK;
 }
 
+// the next pinned slot of the map-update descriptors (and its device twin), free to be rewritten: its copy is three updates old
+static constexpr size_t GRID_SLOT_BYTES =
+    sizeof(GridBuildDesc) * ICP_BATCH_MAX_SEQUENCES + sizeof(NormalsBatchDesc) * ICP_BATCH_MAX_SEQUENCES;
+static int grid_slot_take(icp_batch* b, int* slot_out) {
+    icp_ctx* first = b->members[0];
+    const int slot = b->grid_slot;
+    if (!b->grid_host[slot]) {
+        ICP_HIP(first, hipHostMalloc((void**)&b->grid_host[slot], GRID_SLOT_BYTES, hipHostMallocDefault));
+        ICP_HIP(first, b->grid_dev[slot].reserve(GRID_SLOT_BYTES));
+        ICP_HIP(first, hipEventCreateWithFlags(&b->grid_copied[slot], hipEventDisableTiming));
+    } else {
+        ICP_HIP(first, hipEventSynchronize(b->grid_copied[slot]));  // (three updates ago)
+    }
+    b->grid_slot = (slot + 1) % icp_batch::SLOTS;
+    *slot_out = slot;
+    return ICP_OK;
+}
+
 int icp_batch_map_update(icp_batch* b) {
     if (!b) return ICP_ERR_INVALID_ARGUMENT;
     DeviceGuard device_guard(b->device);
@@ -2282,17 +2301,10 @@ int icp_batch_map_update(icp_batch* b) {
     }
     // the host bookkeeping of every member's update (window, jobs of the rebuild, buffers), the launches of the grid builds
     // left out: their arguments travel to the device in one table, four launches build the B grids
-    const int slot = b->grid_slot;
-    b->grid_slot = (slot + 1) % icp_batch::SLOTS;
-    if (!b->grid_host[slot]) {
-        ICP_HIP(first, hipHostMalloc((void**)&b->grid_host[slot], sizeof(GridBuildDesc) * ICP_BATCH_MAX_SEQUENCES, hipHostMallocDefault));
-        ICP_HIP(first, b->grid_dev[slot].reserve(sizeof(GridBuildDesc) * ICP_BATCH_MAX_SEQUENCES));
-        ICP_HIP(first, hipEventCreateWithFlags(&b->grid_copied[slot], hipEventDisableTiming));
-    } else {
-        ICP_HIP(first, hipEventSynchronize(b->grid_copied[slot]));  // (three updates ago)
-    }
+    int slot = 0;
+    int rc = grid_slot_take(b, &slot);
+    if (rc) return batch_fail(b, rc, first->error);
     GridBuildDesc* table = b->grid_host[slot];
-    int rc = ICP_OK;
     for (int i = 0; i < count; ++i) {
         icp_ctx* ctx = b->members[i];
         if ((rc = continue_launch(ctx, -1))) return batch_fail(b, rc, ctx->error);
@@ -2309,6 +2321,137 @@ int icp_batch_map_update(icp_batch* b) {
         icp_ctx* ctx = b->members[i];
         if ((rc = build_grid_finish(ctx, table[i])) || (rc = map_update_finish(ctx))) return batch_fail(b, rc, ctx->error);
     }
+    return ICP_OK;
+}
+
+static int batch_hip(icp_batch* b, icp_ctx* ctx, hipError_t e, const char* what) {
+    if (e == hipSuccess) return ICP_OK;
+    ctx->error = std::string(what) + ": " + hipGetErrorString(e);
+    return batch_fail(b, ICP_ERR_HIP, ctx->error);
+}
+
+// ICPFrameToModel.__update_map (icp_odometry.py:360-380) for every member: icp_map_update_staged (insert[i] != 0) or the
+// pose-only icp_map_update (insert[i] == 0), each member's host bookkeeping as there — map_update_body with its launches
+// left out — then ONE copy of the descriptors and the launches for all members: the grid builds (launch_grid_build_batch),
+// ONE launch of the neighbourhood lists, ONE launch of the eager normals per neighbourhood size (k_normals_hood2_batch);
+// members whose normals another kernel computes (launch_normals_all's other branches) get their own launch, as there.
+int icp_batch_map_update_staged(icp_batch* b, const float* rel_poses, const int32_t* insert, int64_t* inserted_out) {
+    if (!b) return ICP_ERR_INVALID_ARGUMENT;
+    if (!insert) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched map update: insert[] is required");
+    DeviceGuard device_guard(b->device);
+    const int count = (int)b->members.size();
+    icp_ctx* const* ctxs = b->members.data();
+    icp_ctx* first = ctxs[0];
+    // ---- every member is checked before any member changes (window, map, jobs, grid): a refused call changes nothing
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        { DeviceGuard join_map_stream(ctx); }
+        const std::string who = "batched map update, member " + std::to_string(i) + ": ";
+        if (ctx->stream != first->stream)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "the members must enqueue on one stream (icp_batch_set_stream)");
+        if (insert[i] && ctx->staged_rows < 0)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "no staged cloud (icp_map_stage_cloud)");
+        if (!rel_poses && !ctx->have_device_pose)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "rel_poses = NULL needs a previous registration on every member");
+        if (!rel_poses && insert[i] && ctx->result_pending())
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "rel_poses = NULL with a new cloud: collect the pending "
+                                                                 "registration (icp_batch_register_end) first");
+        const bool first_cloud = ctx->map_m == 0 && ctx->cloud_sizes.empty() && !ctx->grid_valid;  // (the pose is ignored)
+        float inv[16];
+        if (rel_poses && !first_cloud && !invert4(rel_poses + 16 * i, inv))
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "singular relative pose");
+    }
+    // ---- what goes first: iterations held back (the update reads the END of the registrations), the staged counts
+    int rc = batch_flush(b);
+    if (rc) return rc;
+    int64_t staged[ICP_BATCH_MAX_SEQUENCES] = {};
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        if ((rc = continue_launch(ctx, -1)) || (rc = ensure_state(ctx))) return batch_fail(b, rc, ctx->error);
+        if (insert[i]) {  // (long past when the registration was collected in between)
+            if ((rc = batch_hip(b, ctx, hipEventSynchronize(ctx->staged_event), "hipEventSynchronize(staged_event)"))) return rc;
+            staged[i] = *ctx->staged_count_host;
+        }
+    }
+    int slot = 0;
+    if ((rc = grid_slot_take(b, &slot))) return batch_fail(b, rc, first->error);
+    GridBuildDesc* table = b->grid_host[slot];
+    NormalsBatchDesc* ntable = reinterpret_cast<NormalsBatchDesc*>(table + ICP_BATCH_MAX_SEQUENCES);
+    // a member whose bookkeeping has run but whose grid build never reached the stream must not claim that grid (its map
+    // rows are moved by the build's first launch): it reports an empty map until its next update
+    auto invalidate = [&](int upto) {
+        for (int k = 0; k < upto; ++k) {
+            ctxs[k]->grid_valid = false;
+            ctxs[k]->hoods_valid = false;
+            ctxs[k]->normals_ready = false;
+            ctxs[k]->cells_table = nullptr;
+        }
+    };
+    // ---- the host side of every member's update
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        const float* rel = rel_poses ? rel_poses + 16 * i : nullptr;
+        int64_t ins = 0;
+        if (insert[i]) {
+            ctx->staged_rows = -1;  // consumed
+            rc = map_update_body(ctx, rel, ctx->staged_xyz.as<float>(), nullptr, staged[i], true, &ins, staged[i], &table[i]);
+        } else {
+            rc = map_update_body(ctx, rel, nullptr, nullptr, 0, false, &ins, -1, &table[i]);
+        }
+        if (rc) {
+            invalidate(i + 1);
+            return batch_fail(b, rc, ctx->error);
+        }
+        if (inserted_out) inserted_out[i] = ins;
+    }
+    // ---- the eager normals behind the rebuild: map_update_finish's rule, member by member
+    NormalsBatchDesc d11[ICP_BATCH_MAX_SEQUENCES], d6[ICP_BATCH_MAX_SEQUENCES];
+    icp_ctx *c11[ICP_BATCH_MAX_SEQUENCES], *c6[ICP_BATCH_MAX_SEQUENCES], *own[ICP_BATCH_MAX_SEQUENCES];
+    int n11 = 0, n6 = 0, n_own = 0;
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        ctx->hoods_valid = table[i].with_hoods != 0;  // (as build_grid_finish leaves it: the lists are built ahead of every reader)
+        if (!(ctx->have_device_pose && ctx->tgt_n > 0 && wants_eager_normals(ctx, ctx->tgt_n)) || ctx->normals_ready ||
+            ctx->map_m <= 0)
+            continue;
+        if (!normals_batchable(ctx)) {
+            own[n_own++] = ctx;  // (launch_normals_all, as the single update: another kernel, or nothing for another k)
+        } else if (ctx->cfg.num_neighbors_normals + 1 == 11) {
+            normals_batch_desc(ctx, &d11[n11]);
+            c11[n11++] = ctx;
+        } else {
+            normals_batch_desc(ctx, &d6[n6]);
+            c6[n6++] = ctx;
+        }
+    }
+    if (n11) memcpy(ntable, d11, sizeof(NormalsBatchDesc) * (size_t)n11);
+    if (n6) memcpy(ntable + n11, d6, sizeof(NormalsBatchDesc) * (size_t)n6);
+    // ---- one copy, then the launches
+    const size_t bytes = n11 + n6 > 0 ? sizeof(GridBuildDesc) * ICP_BATCH_MAX_SEQUENCES + sizeof(NormalsBatchDesc) * (size_t)(n11 + n6)
+                                      : sizeof(GridBuildDesc) * (size_t)count;
+    const GridBuildDesc* table_dev = b->grid_dev[slot].as<GridBuildDesc>();
+    const NormalsBatchDesc* ntable_dev = reinterpret_cast<const NormalsBatchDesc*>(table_dev + ICP_BATCH_MAX_SEQUENCES);
+    rc = batch_hip(b, first, hipMemcpyAsync(b->grid_dev[slot].ptr, table, bytes, hipMemcpyHostToDevice, first->stream),
+                   "hipMemcpyAsync(descriptors)");
+    if (!rc) rc = batch_hip(b, first, hipEventRecord(b->grid_copied[slot], first->stream), "hipEventRecord(grid_copied)");
+    if (!rc && (rc = launch_grid_build_batch(first, table, table_dev, count))) batch_fail(b, rc, first->error);
+    if (rc) {
+        invalidate(count);
+        return rc;
+    }
+    if ((rc = launch_hood_build_batch(first, table, table_dev, count))) {
+        for (int i = 0; i < count; ++i) ctxs[i]->hoods_valid = false;  // (the grids stand; their normals are not estimated)
+        return batch_fail(b, rc, first->error);
+    }
+    if ((rc = launch_normals_batch(first, 11, d11, ntable_dev, n11)) || (rc = launch_normals_batch(first, 6, d6, ntable_dev + n11, n6)))
+        return batch_fail(b, rc, first->error);
+    for (int k = 0; k < n11 + n6; ++k) {  // (as launch_normals_all)
+        icp_ctx* ctx = k < n11 ? c11[k] : c6[k - n11];
+        ctx->normals_ready = true;
+        ctx->normals_eager_count += ctx->map_m;
+    }
+    for (int k = 0; k < n_own; ++k)
+        if ((rc = map_update_finish(own[k]))) return batch_fail(b, rc, own[k]->error);
     return ICP_OK;
 }
 

@@ -844,15 +844,16 @@ __global__ void k_grid_rows_scatter_batch(const GridBuildDesc* __restrict__ t) {
 // ---------------------------------------------------------------------------------------------------------------------
 static constexpr int HOOD_THREADS = 1024;
 
-__global__ __launch_bounds__(HOOD_THREADS) void k_hood_build(const int* __restrict__ slot_of_cell,
-                                                             const int* __restrict__ ncells_dev, int2* __restrict__ rows,
-                                                             const float4* __restrict__ pts, float4* __restrict__ hood,
-                                                             long long capacity, unsigned long long* __restrict__ used) {
+// (the body of k_hood_build and of k_hood_build_batch: `bx` = the workgroup's index within its map)
+__device__ __forceinline__ void hood_build_body(const int* __restrict__ slot_of_cell, const int* __restrict__ ncells_dev,
+                                                int2* __restrict__ rows, const float4* __restrict__ pts,
+                                                float4* __restrict__ hood, long long capacity,
+                                                unsigned long long* __restrict__ used, int bx) {
     __shared__ int cell_tot[HOOD_THREADS / 32];
     __shared__ unsigned long long base_s;
     const int ncells = *ncells_dev;
-    const int j = blockIdx.x * (HOOD_THREADS / 32) + (threadIdx.x >> 5), c = threadIdx.x & 31;
-    if (blockIdx.x * (HOOD_THREADS / 32) >= ncells) return;  // block-uniform
+    const int j = bx * (HOOD_THREADS / 32) + (threadIdx.x >> 5), c = threadIdx.x & 31;
+    if (bx * (HOOD_THREADS / 32) >= ncells) return;  // block-uniform
     int2 e = make_int2(0, 0);
     size_t row = 0;
     if (j < ncells) {
@@ -901,6 +902,21 @@ __global__ __launch_bounds__(HOOD_THREADS) void k_hood_build(const int* __restri
         if (i < tot) dst[i] = pts[seg_start + (i - seg_excl)];
         else if (i < tot4) dst[i] = make_float4(INFINITY, INFINITY, INFINITY, __int_as_float(0x7fffffff));
     }
+}
+
+__global__ __launch_bounds__(HOOD_THREADS) void k_hood_build(const int* __restrict__ slot_of_cell,
+                                                             const int* __restrict__ ncells_dev, int2* __restrict__ rows,
+                                                             const float4* __restrict__ pts, float4* __restrict__ hood,
+                                                             long long capacity, unsigned long long* __restrict__ used) {
+    hood_build_body(slot_of_cell, ncells_dev, rows, pts, hood, capacity, used, (int)blockIdx.x);
+}
+
+// the lists of B maps in one launch (icp_batch_map_update_staged, api.hip): blockIdx.y = the map, the arguments of
+// k_hood_build in its GridBuildDesc; a map without lists, and the workgroups beyond a map's own count, return at once
+__global__ __launch_bounds__(HOOD_THREADS) void k_hood_build_batch(const GridBuildDesc* __restrict__ t) {
+    const GridBuildDesc& d = t[blockIdx.y];
+    if (!d.with_hoods || blockIdx.x >= (unsigned)((d.m + HOOD_THREADS / 32 - 1) / (HOOD_THREADS / 32))) return;
+    hood_build_body(d.slot_of_cell, d.ncells, d.rows, d.sorted, d.hood, (long long)d.hood_cap, d.hood_used, (int)blockIdx.x);
 }
 
 static unsigned int next_pow2(unsigned int v) {
@@ -1125,6 +1141,7 @@ int build_grid(icp_ctx* ctx, GridBuildDesc* defer) {
     d.pos_of_orig = ctx->pos_of_orig.as<int>();
     d.with_hoods = with_hoods ? 1 : 0;
     d.hood_cap = (unsigned long long)hood_cap;
+    d.hood = with_hoods ? ctx->hood.as<float4>() : (float4*)nullptr;
     // neighbourhood lists for the kNN normals (option "hoods"; maps beyond 2^22 points keep the row walk: 27 x 16 B per
     // point would be gigabytes).  The start of a run is an int: 27 M < 2^31 holds for every map that gets here
     ctx->hoods_valid = false;
@@ -1184,6 +1201,19 @@ int launch_grid_build_batch(icp_ctx* first, const GridBuildDesc* th, const GridB
     if (any_lists) hipLaunchKernelGGL(k_cells_scan_batch, dim3(2, count), dim3(CS_THREADS), 0, first->stream, td);
     if (scan > 0) hipLaunchKernelGGL(k_grid_scan_batch, dim3(scan, count), dim3(SCAN_THREADS), 0, first->stream, td);
     hipLaunchKernelGGL(k_grid_rows_scatter_batch, dim3(scatter, count), dim3(256), 0, first->stream, td);
+    ICP_HIP(first, hipGetLastError());
+    return ICP_OK;
+}
+
+int launch_hood_build_batch(icp_ctx* first, const GridBuildDesc* th, const GridBuildDesc* td, int count) {
+    unsigned hb = 0;
+    for (int b = 0; b < count; ++b) {
+        if (!th[b].with_hoods) continue;
+        const unsigned n = (unsigned)((th[b].m + HOOD_THREADS / 32 - 1) / (HOOD_THREADS / 32));  // (cells <= points)
+        hb = n > hb ? n : hb;
+    }
+    if (hb == 0) return ICP_OK;
+    hipLaunchKernelGGL(k_hood_build_batch, dim3(hb, count), dim3(HOOD_THREADS), 0, first->stream, td);
     ICP_HIP(first, hipGetLastError());
     return ICP_OK;
 }

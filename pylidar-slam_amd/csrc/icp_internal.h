@@ -281,9 +281,19 @@ struct GridBuildDesc {
     unsigned row_blocks;
     float4 *sorted, *csorted, *normals;
     int *nflag, *row_of_pos, *pos_of_orig;
-    // behind the four launches (host side): neighbourhood lists wanted for this build
+    // behind the four launches: neighbourhood lists wanted for this build (k_hood_build; k_hood_build_batch reads them here)
     int with_hoods;
     unsigned long long hood_cap;
+    float4* hood;
+};
+
+// the arguments of k_normals_hood2 for one map of a batched launch (search.hip::k_normals_hood2_batch)
+struct NormalsBatchDesc {
+    GridView g;
+    float4* out;
+    int* nflag;
+    int max_rings;
+    unsigned blocks;  // workgroups of this map (64 points each)
 };
 
 // the arguments of k_pack_targets (grid_sample.hip), as the batched launch reads them from device memory; n = 0: nothing to do
@@ -616,6 +626,8 @@ namespace icp {
 int build_grid(icp_ctx* ctx, GridBuildDesc* defer = nullptr);
 int build_grid_finish(icp_ctx* ctx, const GridBuildDesc& d);  // the neighbourhood lists, where the build wants them
 int launch_grid_build_batch(icp_ctx* first, const GridBuildDesc* table_host, const GridBuildDesc* table_dev, int count);
+// the neighbourhood lists of every map whose prepared build wants them (with_hoods) in ONE launch (nothing to launch: none does)
+int launch_hood_build_batch(icp_ctx* first, const GridBuildDesc* table_host, const GridBuildDesc* table_dev, int count);
 // exclusive scan of n ints (in place allowed); total written to *total_dev (device int) if non-null
 int exclusive_scan_i32(icp_ctx* ctx, const int* in, int* out, int64_t n, int* total_dev);
 // ordered compaction: copies rows (row_floats floats each) whose flag != 0; count to *count_dev
@@ -633,6 +645,13 @@ int launch_normals(icp_ctx* ctx);   // kNN normals for the worklist
 // kNN normals of every map point (eager mode); tail_may_overlap: called at the end of a map update — the stragglers of the
 // estimation may run on the map stream (option "normals_tail_stream")
 int launch_normals_all(icp_ctx* ctx, bool tail_may_overlap = false);
+// ... for B maps at once (icp_batch_map_update_staged): k_normals_hood2_batch<KN>, one NormalsBatchDesc per map in device
+// memory.  normals_batchable: the member's eager normals are what that kernel computes (launch_normals_all otherwise);
+// normals_batch_desc fills its descriptor (behind the member's grid build has been prepared)
+bool normals_batchable(const icp_ctx* ctx);
+void normals_batch_desc(icp_ctx* ctx, NormalsBatchDesc* d);
+int launch_normals_batch(icp_ctx* first, int kn, const NormalsBatchDesc* table_host, const NormalsBatchDesc* table_dev,
+                         int count);
 int launch_gather_neighbors(icp_ctx* ctx, int64_t n, float* pts_out, float* nrm_out, int32_t* idx_out);
 int launch_last_neighbors(icp_ctx* ctx, int iteration, int* out_dev);  // NN cache -> matched map point per target (tests)
 // map-sharded normals: the owned share by original index (zeros elsewhere) / install the all-reduced array

@@ -3436,10 +3436,11 @@ __device__ inline void normal_of_straggler(const GridView& g, int ps, int lane, 
 // the next frame's preprocessing on the caller's stream (api.hip: DeviceGuard's join orders every reader of the normals behind
 // it).  A launch of its own behind this one on the SAME stream was tried in round 4 (+31 us: the 30 us chain per straggler sets
 // the duration of whatever launch runs it); on a stream of its own that chain has ~50 us of independent work to hide behind.
-template <int KN, bool OWNED, bool LIST = false>
-__global__ __launch_bounds__(NRM2_THREADS) void k_normals_hood2(GridView g, int max_rings, int rank, int world,
-                                                                float4* __restrict__ out, int* __restrict__ nflag,
-                                                                int* __restrict__ tail) {
+// (the body of k_normals_hood2 and of its batched form k_normals_hood2_batch: `bx` = the workgroup's index within its map)
+template <int KN, bool OWNED, bool LIST>
+__device__ __forceinline__ void normals_hood2_body(const GridView& g, int max_rings, int rank, int world,
+                                                   float4* __restrict__ out, int* __restrict__ nflag, int* __restrict__ tail,
+                                                   int bx) {
     constexpr int PTS = NRM2_THREADS / 2;
     __shared__ float covs[PTS][7];
     __shared__ int settled[PTS];
@@ -3450,7 +3451,7 @@ __global__ __launch_bounds__(NRM2_THREADS) void k_normals_hood2(GridView g, int 
     if (threadIdx.x == 0) npend = 0;
     __syncthreads();
     const int lq = threadIdx.x >> 1, sub = threadIdx.x & 1;
-    const int s = blockIdx.x * PTS + lq;
+    const int s = bx * PTS + lq;
     bool mine = s < g.m;
     if (OWNED && mine) {
         const float4 P = g.pts[s];
@@ -3475,14 +3476,14 @@ __global__ __launch_bounds__(NRM2_THREADS) void k_normals_hood2(GridView g, int 
         // the dense pass below, which solves them with the rest — the solve was a 5 us chain on one lane per straggler)
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         for (int k = wave; k < npend; k += NRM2_THREADS / 64) {  // wave-uniform
-            const int ps = pend_s[k], slot = ps - blockIdx.x * PTS;
+            const int ps = pend_s[k], slot = ps - bx * PTS;
             normal_of_straggler<KN, OWNED>(g, ps, lane, max_rings, wcov[wave], wl[wave], out, nflag, covs[slot]);
             if (lane == 0) settled[slot] = 1;
         }
         __syncthreads();
     }
     if (threadIdx.x < PTS && settled[threadIdx.x]) {  // the eigen-solves on a dense wave
-        const int s2 = blockIdx.x * PTS + threadIdx.x;
+        const int s2 = bx * PTS + threadIdx.x;
         float nx, ny, nz;
         const float* c = covs[threadIdx.x];
         smallest_eigenvector(c[0], c[1], c[2], c[3], c[4], c[5], nx, ny, nz);
@@ -3493,6 +3494,26 @@ __global__ __launch_bounds__(NRM2_THREADS) void k_normals_hood2(GridView g, int 
             nflag[s2] = 1;
         }
     }
+}
+
+template <int KN, bool OWNED, bool LIST = false>
+__global__ __launch_bounds__(NRM2_THREADS) void k_normals_hood2(GridView g, int max_rings, int rank, int world,
+                                                                float4* __restrict__ out, int* __restrict__ nflag,
+                                                                int* __restrict__ tail) {
+    normals_hood2_body<KN, OWNED, LIST>(g, max_rings, rank, world, out, nflag, tail, (int)blockIdx.x);
+}
+
+// The eager normals behind a batched map update (icp_batch_map_update_staged, api.hip) for B maps in ONE launch: blockIdx.y =
+// the map, its arguments in a NormalsBatchDesc in device memory; the workgroups beyond a map's own count return at once.  The
+// body is k_normals_hood2's (stragglers finished inside the launch, a wave each): the same normals, bit for bit.
+template <int KN>
+__global__ __launch_bounds__(NRM2_THREADS) void k_normals_hood2_batch(const NormalsBatchDesc* __restrict__ t) {
+    const NormalsBatchDesc& d = t[blockIdx.y];
+    if (blockIdx.x >= d.blocks) return;  // (block-uniform)
+    // (the view copied out of the table once: read through the reference, its fields were reloaded where the body uses them
+    // — 164 VGPRs instead of k_normals_hood2's 98)
+    const GridView g = d.g;
+    normals_hood2_body<KN, false, false>(g, d.max_rings, 0, 1, d.out, d.nflag, nullptr, (int)blockIdx.x);
 }
 
 // The stragglers of k_normals_hood2<.., LIST> — map points whose KN-th neighbour the pair pass does not certify, 0.3 % of a
@@ -4014,6 +4035,34 @@ int launch_normals_all(icp_ctx* ctx, bool tail_may_overlap) {
     ICP_HIP(ctx, hipGetLastError());
     ctx->normals_ready = true;
     ctx->normals_eager_count += ctx->map_m;
+    return ICP_OK;
+}
+
+// ---- the eager normals of B maps in one launch per neighbourhood size (icp_batch_map_update_staged, api.hip)
+// the members launch_normals_all would serve with k_normals_hood2<KN, false> (stragglers inside the launch), unprofiled
+bool normals_batchable(const icp_ctx* ctx) {
+    const int kn = ctx->cfg.num_neighbors_normals + 1;
+    return (kn == 11 || kn == 6) && ctx->knn_lanes != 2 && ctx->hoods >= 2 && ctx->hoods_valid && ctx->hood.ptr &&
+           !ctx->normals_list && !ctx->normals_tail_stream && !ctx->prof.enabled && !ctx->search_stats && ctx->map_m > 0;
+}
+
+void normals_batch_desc(icp_ctx* ctx, NormalsBatchDesc* d) {
+    d->g = make_view(ctx);
+    d->out = ctx->normals.as<float4>();
+    d->nflag = ctx->nflag.as<int>();
+    d->max_rings = knn_fine_rings(ctx);
+    d->blocks = (unsigned)((ctx->map_m + NRM2_THREADS / 2 - 1) / (NRM2_THREADS / 2));
+}
+
+int launch_normals_batch(icp_ctx* first, int kn, const NormalsBatchDesc* th, const NormalsBatchDesc* td, int count) {
+    if (count <= 0) return ICP_OK;
+    unsigned blocks = 0;
+    for (int b = 0; b < count; ++b) blocks = th[b].blocks > blocks ? th[b].blocks : blocks;
+    if (kn == 11)
+        hipLaunchKernelGGL((k_normals_hood2_batch<11>), dim3(blocks, count), dim3(NRM2_THREADS), 0, first->stream, td);
+    else
+        hipLaunchKernelGGL((k_normals_hood2_batch<6>), dim3(blocks, count), dim3(NRM2_THREADS), 0, first->stream, td);
+    ICP_HIP(first, hipGetLastError());
     return ICP_OK;
 }
 

@@ -15,7 +15,7 @@ def __getattr__(name):
     if name in ("IcpContext", "InvalidJacobianError", "RegisterResult"):
         from . import engine
         return getattr(engine, name)
-    if name in ("MI355XICPFrameToModel", "MI355XICPConfig", "HashGridLocalMap", "PointToPlaneAlignment",
+    if name in ("MI355XICPFrameToModel", "MI355XICPFrameToModelBatch", "MI355XICPConfig", "HashGridLocalMap", "PointToPlaneAlignment",
                 "SphericalProjector", "GridSample", "GridSampleConfig", "grid_sample",
                 "ConstantVelocityInitialization", "OdometryAlgorithm"):
         from . import odometry

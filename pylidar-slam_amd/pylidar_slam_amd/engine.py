@@ -849,6 +849,31 @@ class IcpBatch:
         """`map_update(None)` on every member: the pose-only update by the device-resident pose of its registration."""
         self._check(self._lib.icp_batch_map_update(self._h))
 
+    def stage(self, clouds, skip_null: bool = False):
+        """`IcpContext.map_stage_cloud(clouds[b])` on every member (one staging call each): the clouds a later
+        `map_update_staged` inserts."""
+        if len(clouds) != len(self.contexts):
+            raise AssertionError(f"expected {len(self.contexts)} clouds, got {len(clouds)}")
+        for c, pts in zip(self.contexts, clouds):
+            c.map_stage_cloud(pts, skip_null=skip_null)
+
+    def map_update_staged(self, insert, rel_poses=None):
+        """`ICPFrameToModel.__update_map` for every member (icp_batch_map_update_staged): member b inserts the cloud it
+        staged (`stage`) if `insert[b]`, and is updated by its pose only otherwise.  `rel_poses`: B 4x4 matrices, or None
+        (every member's device-resident pose of its last registration).  Returns the rows inserted per member."""
+        b = len(self.contexts)
+        if len(insert) != b:
+            raise AssertionError(f"expected {b} insert flags, got {len(insert)}")
+        flags = (C.c_int32 * b)(*[1 if f else 0 for f in insert])
+        rel = None
+        if rel_poses is not None:
+            rel = np.ascontiguousarray(np.stack([np.asarray(m, dtype=np.float32).reshape(16) for m in rel_poses]))
+            if rel.shape[0] != b:
+                raise AssertionError("one relative pose per member")
+        ins = (C.c_int64 * b)()
+        self._check(self._lib.icp_batch_map_update_staged(self._h, rel.ctypes.data if rel is not None else None, flags, ins))
+        return [int(v) for v in ins]
+
     def register_end(self):
         """One wait for all members; a list of `RegisterResult`s (raises what the first failing member would raise)."""
         b = len(self.contexts)

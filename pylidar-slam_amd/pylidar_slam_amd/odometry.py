@@ -26,13 +26,14 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 import torch
 
-from .engine import IcpContext, InvalidJacobianError, RegisterResult  # noqa: F401
+from .engine import IcpBatch, IcpContext, InvalidJacobianError, RegisterResult  # noqa: F401
 
 __all__ = ["OdometryAlgorithm", "MI355XICPConfig", "MI355XICPFrameToModel", "HashGridLocalMap",
            "HashGridLocalMapConfig", "ProjectiveLocalMap", "ProjectiveLocalMapConfig", "PointToPlaneAlignment",
            "PointToPlaneAlignmentConfig", "PointToPointAlignment", "PointToPointAlignmentConfig", "SphericalProjector",
            "GridSample", "GridSampleConfig", "grid_sample", "Distortion", "DistortionConfig", "Voxelization",
            "VoxelizationConfig", "ToDevice", "ToDeviceConfig", "ConstantVelocityInitialization", "NeighborhoodResult",
+           "MI355XICPFrameToModelBatch",
            "build_pose_matrix", "from_pose_matrix"]
 
 
@@ -1065,3 +1066,104 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         if len(self.relative_poses) == 0:
             return None
         return np.concatenate(self.relative_poses, axis=0)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+class MI355XICPFrameToModelBatch:
+    """B independent sequences of `MI355XICPFrameToModel` (kd-tree style map, point-to-plane) advanced together: one call
+    takes the next frame of every sequence, registers all of them with one launch per ICP iteration (`IcpBatch`) and
+    updates all B maps — key-frame insertion, eviction, grid rebuild and eager normals — with one `map_update_staged`.
+    Per sequence the same poses, iteration counts, maps and normals, bit for bit, as `MI355XICPFrameToModel` on the same
+    frames (ICPFrameToModel.do_process_next_frame, slam/odometry/icp_odometry.py:157-246; __update_map :360-380).
+
+    Input: torch tensors (the device-resident preprocessing of config/slam/preprocessing/grid_sample_mi355x.yaml).
+    Per member still: the projection, the staging of the frame's rows and the frame-0 insertion of the vertex map."""
+
+    def __init__(self, config: MI355XICPConfig, count: int, projector=None, device=None, **kwargs):
+        assert_debug(int(count) >= 1, "a batch needs at least one sequence")
+        self.members = [MI355XICPFrameToModel(config, projector=projector, device=device, **kwargs) for _ in range(int(count))]
+        m0 = self.members[0]
+        self.config = m0.config
+        assert_debug(not m0._projective, "MI355XICPFrameToModelBatch batches the kd-tree style local map only "
+                                         "(kdtree_local_map / hashgrid_local_map), not the projective map")
+        assert_debug(not m0._point_to_point, "MI355XICPFrameToModelBatch batches the point-to-plane alignment only "
+                                             "(point_to_plane_gauss_newton), not point-to-point")
+        self.batch = IcpBatch([m.ctx for m in self.members])
+        self.device = m0.device
+        self._iter = 0
+        self.elapsed: list = []
+
+    def __len__(self):
+        return len(self.members)
+
+    def init(self):
+        for m in self.members:
+            m.init()
+        self._iter = 0
+        self.elapsed = []
+
+    def get_relative_poses(self, b: int) -> Optional[np.ndarray]:
+        return self.members[b].get_relative_poses()
+
+    def get_elapsed(self) -> float:
+        return sum(self.elapsed)
+
+    def process_next_frames(self, data_dicts):
+        """`data_dicts[b]`: the next frame of sequence b (its preprocessed points under `config.data_key` as a torch tensor,
+        its initial estimate under `init_rpose` as for the single plugin); fills `odometry_pose` and `odometry_pc` of every
+        dict, as MI355XICPFrameToModel.process_next_frame does."""
+        beginning = time.time()
+        self._process(data_dicts)
+        self.elapsed.append(time.time() - beginning)
+
+    def _process(self, data_dicts):
+        members = self.members
+        assert_debug(len(data_dicts) == len(members), f"expected {len(members)} frames, got {len(data_dicts)}")
+        key = self.config.data_key
+        for d in data_dicts:
+            assert_debug(key in d, f"Could not find the key `{key}` in the input dictionary.")
+            assert_debug(isinstance(d[key], torch.Tensor),
+                         "MI355XICPFrameToModelBatch takes torch tensors (device-resident preprocessing), not numpy input")
+        self.batch.use_torch_stream()
+        for m, d in zip(members, data_dicts):
+            m._read_input(d)  # the projection, per member
+        if self._iter == 0:
+            eye = np.eye(4, dtype=np.float32)
+            for m in members:  # :176
+                m.local_map.update(eye, new_vertex_map=m._tgt_vmap.unsqueeze(0))
+                m.relative_poses.append(eye[None])
+                m.absolute_poses.append(np.eye(4, dtype=np.float64))
+                m._iter += 1
+            self._iter += 1
+            return
+        inits = [m._initial_pose(d) for m, d in zip(members, data_dicts)]
+        sampled = [m.sample_points() for m in members]
+        assert_debug(len({s for _, s in sampled}) == 1 and len({m._pc_is_pixels for m in members}) == 1,
+                     "the frames of one batched call must be all point clouds or all vertex maps")
+        # the frames go into the maps right after their registration (:229-231): compacted and counted in front of it
+        self.batch.stage([m._tgt_pc.reshape(-1, 3) for m in members], skip_null=members[0]._pc_is_pixels)
+        want = ["distorted" not in d for d in data_dicts]
+        ready = [m._rows_event() if w else None for m, w in zip(members, want)]
+        self.batch.register_launch([t for t, _ in sampled], inits, skip_null=sampled[0][1])
+        pcs = [m._rows_to_host(r) if w else d["distorted"] for m, r, w, d in zip(members, ready, want, data_dicts)]
+        results = self.batch.register_end()  # raises before a map is touched (:286)
+        # the key-frame decisions, each with __update_map's own arithmetic (:360-380)
+        insert = []
+        for m, res in zip(members, results):
+            new_delta = (m._delta_since_map_update @ res.pose).astype(np.float32)
+            dp = from_pose_matrix(new_delta)
+            key_frame = bool(np.linalg.norm(dp[:3]) > m._register_threshold_trans or
+                             np.linalg.norm(dp[3:]) * 180 / np.pi > m._register_threshold_rot)
+            m._delta_since_map_update = np.eye(4, dtype=np.float32) if key_frame else new_delta
+            insert.append(key_frame)
+        inserted = self.batch.map_update_staged(insert, [res.pose for res in results])
+        for m, res, d, pc, ins, key_frame in zip(members, results, data_dicts, pcs, inserted, insert):
+            m.last_result = res
+            if key_frame:
+                m.local_map._last_count = ins
+            m.relative_poses.append(res.pose[None].copy())
+            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
+            d[m.pointcloud_key()] = pc  # :243
+            d[m.relative_pose_key()] = res.pose.reshape(4, 4).copy()  # :244
+            m._iter += 1
+        self._iter += 1
