@@ -489,6 +489,31 @@ int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
  *                              member is on another stream, an inserting member has no staged cloud, or rel_poses = NULL while a
  *                              member never registered or an inserting member's registration has not been collected
  *                              (icp_batch_register_end).  Held-back iterations are enqueued first;
+ *   icp_batch_pmap_register_launch  icp_pmap_register (the reference's ProjectiveLocalMap.nearest_neighbor_search + the
+ *                              Gauss-Newton step per ICP iteration, slam/odometry/local_map.py:205-235, icp_odometry.py:248-299)
+ *                              against every member's projective map, enqueued, collected by icp_batch_register_end:
+ *                              xyz[b] / n[b] = member b's targets, init_poses = count x 16 floats or NULL (identity), or
+ *                              from_last = 1 (the device-resident pose of the member's previous registration).  All
+ *                              max_num_alignments iterations are enqueued for all members — ONE launch in front (targets,
+ *                              states, z-buffers), then three per iteration (projection of the targets, association + rows +
+ *                              partial sums, sum + solve) — a member whose loop has ended does nothing on the device; no host
+ *                              polls.  Per member the same result, losses and steps, bit for bit, as icp_pmap_register on that
+ *                              member alone.  Every member is checked before any changes: ICP_ERR_EMPTY_MAP when a member has
+ *                              no projective map; ICP_ERR_INVALID_ARGUMENT when members are on different streams, differ in
+ *                              max_num_alignments, scheme, sigma, height, width or field of view, a member's registration is
+ *                              still pending (icp_batch_register_end / icp_register_end first) or a member holds kd-tree
+ *                              iterations back (chunked launches), or runs point-to-point, an exchange or profiling;
+ *   icp_batch_pmap_update      icp_pmap_update (ProjectiveLocalMap.update, slam/odometry/local_map.py:122-202) for every member:
+ *                              rel_poses = count x 16 floats (required); vmaps[b] ([3,H,W], `mem`) inserts member b's vertex
+ *                              map with its normal map (normals_kernel_size), vmaps[b] = NULL (or vmaps = NULL) is a pose-only
+ *                              update; the first update of an empty map needs a vertex map.  The window (poses re-expressed in
+ *                              double precision, eviction beyond local_map_size) is kept on the host as icp_pmap_update keeps
+ *                              it; on the device ONE launch inserts the new maps (normal map fused with the store), three
+ *                              rebuild the models of every (member, slot) pair, whatever the window size.  Per member the same
+ *                              window and model, bit for bit, as icp_pmap_update on that member alone.  Every member is checked
+ *                              before any changes (ICP_ERR_INVALID_ARGUMENT, nothing changed): one stream, one image geometry,
+ *                              no pending registration, no held-back kd-tree iterations, a vertex map for an empty map, a
+ *                              regular relative pose;
  *   icp_batch_register_end     icp_register_end for every member (results[b]; loss_per_iter_out / dx_per_iter_out:
  *                              count x max_num_alignments (x 6) entries or NULL): ONE wait for all of them.  Returns the
  *                              first member's non-zero status, every member's own in results[b].status. */
@@ -503,6 +528,10 @@ int icp_batch_register_launch(icp_batch* batch, const float* const* xyz, const i
 int icp_batch_project(icp_batch* batch, const float* const* xyz, const int64_t* n, float* const* vmap_out);
 int icp_batch_map_update(icp_batch* batch);
 int icp_batch_map_update_staged(icp_batch* batch, const float* rel_poses, const int32_t* insert, int64_t* inserted_out);
+int icp_batch_pmap_register_launch(icp_batch* batch, const float* const* xyz, const int64_t* n, int mem, int target_mode,
+                                   const float* init_poses, int from_last);
+int icp_batch_pmap_update(icp_batch* batch, const float* rel_poses, const float* const* vmaps, int mem,
+                          int normals_kernel_size);
 int icp_batch_register_end(icp_batch* batch, icp_register_result* results, double* loss_per_iter_out,
                            float* dx_per_iter_out);
 

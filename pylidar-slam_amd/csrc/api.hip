@@ -1152,6 +1152,70 @@ int icp_pmap_init(icp_ctx* ctx) {
 
 int icp_pmap_num_maps(const icp_ctx* ctx) { return ctx ? (int)ctx->pm_slots.size() : 0; }
 
+// ProjectiveLocalMap.update's window on the host (local_map.py:139-171), shared by icp_pmap_update and
+// icp_batch_pmap_update.  pmap_window_check: would the update be refused (nothing changes)?
+static int pmap_window_check(const icp_ctx* ctx, const float rel_pose[16], bool insert, const char** why) {
+    if (ctx->pm_slots.empty()) {
+        if (!insert) {
+            *why = "the first update needs a vertex map";
+            return ICP_ERR_INVALID_ARGUMENT;
+        }
+        return ICP_OK;
+    }
+    float inv[16];
+    if (!invert4(rel_pose, inv)) {
+        *why = "singular relative pose";
+        return ICP_ERR_INVALID_ARGUMENT;
+    }
+    return ICP_OK;
+}
+
+// the storage slot a new vertex map goes to (the window is unchanged): -1 when none is free
+static int pmap_free_slot(const icp_ctx* ctx) {
+    const int cap = ctx->cfg.local_map_size + 1;
+    for (int s = 0; s < cap; ++s) {
+        bool used = false;
+        for (int u : ctx->pm_slots) used |= (u == s);
+        if (!used) return s;
+    }
+    return -1;
+}
+
+// the window step of a checked update: every kept pose re-expressed by inv(rel_pose) in double precision, the map stored in
+// `slot` appended (slot < 0: a pose-only update), the oldest dropped beyond local_map_size
+static void pmap_window_step(icp_ctx* ctx, const float rel_pose[16], int slot) {
+    if (ctx->pm_slots.empty()) {
+        icp_ctx::PmPose p;
+        memcpy(p.m, rel_pose, sizeof(p.m));  // `_local_map_poses = relative_pose` (local_map.py:147)
+        ctx->pm_slots.push_back(slot);
+        ctx->pm_poses.push_back(p);
+        return;
+    }
+    float inv[16];
+    (void)invert4(rel_pose, inv);
+    for (auto& p : ctx->pm_poses) {  // old_poses = relative_pose.inverse() @ poses (:149)
+        float out[16];
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) {
+                double a = 0.0;
+                for (int k = 0; k < 4; ++k) a += (double)inv[4 * r + k] * (double)p.m[4 * k + c];
+                out[4 * r + c] = (float)a;
+            }
+        memcpy(p.m, out, sizeof(out));
+    }
+    if (slot >= 0) {
+        icp_ctx::PmPose eye;
+        memset(eye.m, 0, sizeof(eye.m));
+        eye.m[0] = eye.m[5] = eye.m[10] = eye.m[15] = 1.f;
+        ctx->pm_slots.push_back(slot);
+        ctx->pm_poses.push_back(eye);
+    }
+    if ((int)ctx->pm_poses.size() > ctx->cfg.local_map_size) {  // :166-171
+        ctx->pm_slots.erase(ctx->pm_slots.begin());
+        ctx->pm_poses.erase(ctx->pm_poses.begin());
+    }
+}
+
 int icp_pmap_update(icp_ctx* ctx, const float rel_pose[16], const float* vmap, int mem, int normals_kernel_size) {
     DeviceGuard device_guard(ctx);
     if (!ctx || !rel_pose) return ICP_ERR_INVALID_ARGUMENT;
@@ -1159,6 +1223,8 @@ int icp_pmap_update(icp_ctx* ctx, const float rel_pose[16], const float* vmap, i
         return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "normals_kernel_size must be odd, 1..15");
     int rc = ensure_state(ctx);
     if (rc) return rc;
+    const char* why = nullptr;
+    if ((rc = pmap_window_check(ctx, rel_pose, vmap != nullptr, &why))) return fail(ctx, rc, why);
     const size_t bytes = (size_t)ctx->cfg.height * ctx->cfg.width * 12;
     const void* in = nullptr;
     if (vmap) {
@@ -1166,50 +1232,12 @@ int icp_pmap_update(icp_ctx* ctx, const float rel_pose[16], const float* vmap, i
         ICP_HIP(ctx, ctx->pm_tmp.reserve(bytes));
         if ((rc = normal_map_device(ctx, (const float*)in, normals_kernel_size, ctx->pm_tmp.as<float>()))) return rc;
     }
-    const int cap = ctx->cfg.local_map_size + 1;
-    auto free_slot = [&]() {
-        for (int s = 0; s < cap; ++s) {
-            bool used = false;
-            for (int u : ctx->pm_slots) used |= (u == s);
-            if (!used) return s;
-        }
-        return -1;
-    };
-    if (ctx->pm_slots.empty()) {
-        if (!vmap) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "the first update needs a vertex map");
-        icp_ctx::PmPose p;
-        memcpy(p.m, rel_pose, sizeof(p.m));  // `_local_map_poses = relative_pose` (local_map.py:147)
-        if ((rc = pmap_store_slot(ctx, 0, (const float*)in, ctx->pm_tmp.as<float>()))) return rc;
-        ctx->pm_slots.push_back(0);
-        ctx->pm_poses.push_back(p);
-    } else {
-        float inv[16];
-        if (!invert4(rel_pose, inv)) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "singular relative pose");
-        for (auto& p : ctx->pm_poses) {  // old_poses = relative_pose.inverse() @ poses (:149)
-            float out[16];
-            for (int r = 0; r < 4; ++r)
-                for (int c = 0; c < 4; ++c) {
-                    double a = 0.0;
-                    for (int k = 0; k < 4; ++k) a += (double)inv[4 * r + k] * (double)p.m[4 * k + c];
-                    out[4 * r + c] = (float)a;
-                }
-            memcpy(p.m, out, sizeof(out));
-        }
-        if (vmap) {
-            const int slot = free_slot();
-            if (slot < 0) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "no free projective-map slot");
-            if ((rc = pmap_store_slot(ctx, slot, (const float*)in, ctx->pm_tmp.as<float>()))) return rc;
-            icp_ctx::PmPose eye;
-            memset(eye.m, 0, sizeof(eye.m));
-            eye.m[0] = eye.m[5] = eye.m[10] = eye.m[15] = 1.f;
-            ctx->pm_slots.push_back(slot);
-            ctx->pm_poses.push_back(eye);
-        }
-        if ((int)ctx->pm_poses.size() > ctx->cfg.local_map_size) {  // :166-171
-            ctx->pm_slots.erase(ctx->pm_slots.begin());
-            ctx->pm_poses.erase(ctx->pm_poses.begin());
-        }
+    int slot = -1;
+    if (vmap) {
+        if ((slot = pmap_free_slot(ctx)) < 0) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "no free projective-map slot");
+        if ((rc = pmap_store_slot(ctx, slot, (const float*)in, ctx->pm_tmp.as<float>()))) return rc;
     }
+    pmap_window_step(ctx, rel_pose, slot);
     if ((rc = pmap_build(ctx))) return rc;
     if (vmap && mem == ICP_MEM_HOST) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ICP_OK;
@@ -1272,6 +1300,7 @@ int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int ta
     ctx->tgt_mode = target_mode;
     if ((rc = prepare_targets_and_state(ctx, n, init_pose))) return rc;
     ctx->have_device_pose = false;  // icp_map_update(rel_pose = NULL) follows a registration against the kd-tree style map only
+    ctx->pm_have_pose = true;
     ctx->in_registration = true;
     const int iters = ctx->cfg.max_num_alignments;
     const int poll = ctx->cfg.threshold_delta_pose > 0.f ? ctx->cfg.poll_every : 0;
@@ -2054,6 +2083,26 @@ int icp_batch_set_stream(icp_batch* b, void* hip_stream) {
     return ICP_OK;
 }
 
+// the next pinned descriptor slot (and its device twin) with room for `need` bytes, free to be rewritten: its copy has left
+static int table_slot_take(icp_batch* b, size_t need, int* slot_out) {
+    icp_ctx* first = b->members[0];
+    const int slot = b->slot;
+    b->slot = (slot + 1) % icp_batch::SLOTS;
+    if (b->host_bytes[slot] < need) {
+        if (b->copied[slot]) ICP_HIP(first, hipEventSynchronize(b->copied[slot]));
+        if (b->host[slot]) (void)hipHostFree(b->host[slot]);
+        b->host[slot] = nullptr;
+        b->host_bytes[slot] = 0;
+        ICP_HIP(first, hipHostMalloc((void**)&b->host[slot], need, hipHostMallocDefault));
+        b->host_bytes[slot] = need;
+    }
+    ICP_HIP(first, b->dev[slot].reserve(need));
+    if (!b->copied[slot]) ICP_HIP(first, hipEventCreateWithFlags(&b->copied[slot], hipEventDisableTiming));
+    else ICP_HIP(first, hipEventSynchronize(b->copied[slot]));  // (three chunks ago: long past)
+    *slot_out = slot;
+    return ICP_OK;
+}
+
 // Enqueues the next `chunk` iterations of the batch's registration in progress (all that are left when chunk < 0): their
 // descriptor tables into a fresh pinned slot, one copy, the launches; behind the chunk's last iteration a summing / solving
 // launch that also delivers every member's result block; ONE event behind it all.  `packs` (first chunk only): the target
@@ -2067,23 +2116,12 @@ static int batch_enqueue(icp_batch* b, int chunk, const PackDesc* packs, bool fi
     if (chunk <= 0) return ICP_OK;
     const int it_begin = b->run_next, it_end = it_begin + chunk;
     const bool lead = b->run_lead;
-    int rc = ICP_OK;
-    const int slot = b->slot;
-    b->slot = (slot + 1) % icp_batch::SLOTS;
     const size_t it_bytes = iterate_desc_bytes() * (size_t)count, ss_bytes = sum_solve_desc_bytes() * (size_t)count;
     const size_t pack_bytes = ((sizeof(PackDesc) * (size_t)count + 255) / 256) * 256;  // the packing launch's table leads the slot
     const size_t need = pack_bytes + (size_t)chunk * (it_bytes + ss_bytes);
-    if (b->host_bytes[slot] < need) {
-        if (b->copied[slot]) ICP_HIP(first, hipEventSynchronize(b->copied[slot]));
-        if (b->host[slot]) (void)hipHostFree(b->host[slot]);
-        b->host[slot] = nullptr;
-        b->host_bytes[slot] = 0;
-        ICP_HIP(first, hipHostMalloc((void**)&b->host[slot], need, hipHostMallocDefault));
-        b->host_bytes[slot] = need;
-    }
-    ICP_HIP(first, b->dev[slot].reserve(need));
-    if (!b->copied[slot]) ICP_HIP(first, hipEventCreateWithFlags(&b->copied[slot], hipEventDisableTiming));
-    else ICP_HIP(first, hipEventSynchronize(b->copied[slot]));  // (three chunks ago: long past)
+    int slot = 0;
+    int rc = table_slot_take(b, need, &slot);
+    if (rc) return batch_fail(b, rc, first->error);
     for (int i = 0; i < count; ++i) {
         ctxs[i]->in_registration = true;
         if ((rc = result_fold_begin(ctxs[i], !first_chunk))) return batch_fail(b, rc, ctxs[i]->error);
@@ -2452,6 +2490,218 @@ int icp_batch_map_update_staged(icp_batch* b, const float* rel_poses, const int3
     }
     for (int k = 0; k < n_own; ++k)
         if ((rc = map_update_finish(own[k]))) return batch_fail(b, rc, own[k]->error);
+    return ICP_OK;
+}
+
+// ---- the projective local map, B maps per launch -------------------------------------------------------------------
+// What every batched projective call asks of its members: one stream, one image geometry (the kernels share the pixel grid
+// and the projection), nothing of a registration still open, no kd-tree iterations held back.  Nothing changes on refusal.
+static int pmap_batch_check(icp_batch* b, const char* what) {
+    icp_ctx* first = b->members[0];
+    for (size_t i = 0; i < b->members.size(); ++i) {
+        icp_ctx* ctx = b->members[i];
+        { DeviceGuard join_map_stream(ctx); }
+        const std::string who = std::string(what) + ", member " + std::to_string(i) + ": ";
+        if (ctx->stream != first->stream)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "the members must enqueue on one stream (icp_batch_set_stream)");
+        if (ctx->cfg.height != first->cfg.height || ctx->cfg.width != first->cfg.width || ctx->cfg.up_fov != first->cfg.up_fov ||
+            ctx->cfg.down_fov != first->cfg.down_fov)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "the members must share height, width and field of view");
+        if (ctx->in_registration || ctx->result_pending())
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "a registration is still pending: collect it first "
+                                                                 "(icp_batch_register_end / icp_register_end)");
+        if (ctx->batch_hold || ctx->launch_remaining > 0)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "kd-tree iterations are still held back: collect them first");
+    }
+    return ICP_OK;
+}
+
+int icp_batch_pmap_register_launch(icp_batch* b, const float* const* xyz, const int64_t* n, int mem, int target_mode,
+                                   const float* init_poses, int from_last) {
+    if (!b || !xyz || !n) return ICP_ERR_INVALID_ARGUMENT;
+    DeviceGuard device_guard(b->device);
+    const int count = (int)b->members.size();
+    icp_ctx* const* ctxs = b->members.data();
+    icp_ctx* first = ctxs[0];
+    const int iters = first->cfg.max_num_alignments;
+    // ---- every member is checked before any member changes
+    int rc = pmap_batch_check(b, "batched projective registration");
+    if (rc) return rc;
+    int max_n = 0;
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        const std::string who = "batched projective registration, member " + std::to_string(i) + ": ";
+        if (n[i] < 0 || (n[i] > 0 && !xyz[i])) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "no scan");
+        if (ctx->cfg.max_num_alignments != iters || ctx->cfg.scheme != first->cfg.scheme || ctx->cfg.sigma != first->cfg.sigma)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "the members must share max_num_alignments, scheme and sigma");
+        if (ctx->exchange_on || ctx->prof.enabled || ctx->cost != ICP_COST_POINT_TO_PLANE)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "point-to-plane registrations without exchange or profiling only");
+        if (ctx->pm_slots.empty()) return batch_fail(b, ICP_ERR_EMPTY_MAP, who + "the projective local map is empty");
+        if (from_last && !ctx->pm_have_pose && !ctx->have_device_pose)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "no previous registration to start from");
+        max_n = std::max(max_n, (int)n[i]);
+    }
+    struct Unwind {  // an error below leaves no member "in registration"
+        icp_batch* b;
+        bool armed = true;
+        ~Unwind() {
+            if (!armed) return;
+            for (icp_ctx* ctx : b->members) {
+                ctx->in_registration = false;
+                ctx->result_fold_to = nullptr;
+                ctx->result_folded = false;
+            }
+        }
+    } unwind{b};
+    // ---- descriptor slot: [packs | registrations | sum + solve | sum + solve of the last iteration]
+    const size_t pad = 256;
+    const size_t pack_bytes = ((sizeof(PackDesc) * (size_t)count + pad - 1) / pad) * pad;
+    const size_t reg_bytes = ((pmap_reg_desc_bytes() * (size_t)count + pad - 1) / pad) * pad;
+    const size_t ss_bytes = ((sum_solve_desc_bytes() * (size_t)count + pad - 1) / pad) * pad;
+    const size_t need = pack_bytes + reg_bytes + 2 * ss_bytes;
+    int slot = 0;
+    if ((rc = table_slot_take(b, need, &slot))) return batch_fail(b, rc, first->error);
+    char* host = b->host[slot];
+    int rows[ICP_BATCH_MAX_SEQUENCES], quad[ICP_BATCH_MAX_SEQUENCES];
+    // ---- every member as icp_pmap_register begins it, the packing launch left to the batch
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        if ((rc = ensure_state(ctx))) return batch_fail(b, rc, ctx->error);
+        const void* in;
+        if ((rc = import_buffer(ctx, xyz[i], (size_t)n[i] * 12, mem, ctx->targets, &in))) return batch_fail(b, rc, ctx->error);
+        ctx->tgt_ptr = (const float*)in;
+        ctx->tgt_n = n[i];
+        ctx->tgt_mode = target_mode;
+        PackDesc* pack = reinterpret_cast<PackDesc*>(host) + i;
+        const float* init = (init_poses && !from_last) ? init_poses + 16 * i : nullptr;
+        if ((rc = prepare_targets_and_state(ctx, n[i], init, from_last != 0, pack))) return batch_fail(b, rc, ctx->error);
+        ctx->have_device_pose = false;  // (as icp_pmap_register)
+        ctx->in_registration = true;
+        if ((rc = pmap_register_desc(ctx, host + pack_bytes + pmap_reg_desc_bytes() * i, &rows[i])))
+            return batch_fail(b, rc, ctx->error);
+        quad[i] = 1;
+        if ((rc = result_fold_begin(ctx, false))) return batch_fail(b, rc, ctx->error);
+    }
+    char* ss_host = host + pack_bytes + reg_bytes;
+    prepare_sum_solve_batch(ctxs, count, rows, quad, false, false, ss_host);
+    if (iters > 0)  // (the last iteration's launch delivers the result blocks; without iterations a copy does)
+        prepare_sum_solve_batch(ctxs, count, rows, quad, false, true, ss_host + ss_bytes);
+    // ---- one copy, then the launches: targets + states + z-buffers, and three per iteration
+    const char* dev = b->dev[slot].as<char>();
+    ICP_HIP(first, hipMemcpyAsync(b->dev[slot].ptr, host, need, hipMemcpyHostToDevice, first->stream));
+    ICP_HIP(first, hipEventRecord(b->copied[slot], first->stream));
+    if ((rc = pmap_launch_begin_batch(first, reinterpret_cast<const PackDesc*>(dev), dev + pack_bytes, count, max_n)))
+        return batch_fail(b, rc, first->error);
+    for (int it = 0; it < iters; ++it) {
+        if ((rc = pmap_launch_iteration_batch(first, dev + pack_bytes, count, max_n)) ||
+            (rc = launch_sum_solve_batch(first, count, dev + pack_bytes + reg_bytes + (it + 1 == iters ? ss_bytes : 0))))
+            return batch_fail(b, rc, first->error);
+    }
+    // ---- the results: ONE event behind every member's block (icp_batch_register_end)
+    const int done_slot = b->done_next;
+    b->done_next ^= 1;
+    hipEvent_t& done = b->done[done_slot];
+    if (!done) ICP_HIP(first, hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        ctx->launch_enqueued = iters;
+        ctx->launch_remaining = 0;
+        ctx->batch_hold = false;
+        if ((rc = enqueue_result_copy(ctx, false, done))) return batch_fail(b, rc, ctx->error);
+        ctx->result_fold_to = nullptr;
+        ctx->result_folded = false;
+        ctx->in_registration = false;  // the result waits in its slot
+        ctx->pm_have_pose = true;
+    }
+    ICP_HIP(first, hipEventRecord(done, first->stream));
+    unwind.armed = false;
+    return ICP_OK;
+}
+
+int icp_batch_pmap_update(icp_batch* b, const float* rel_poses, const float* const* vmaps, int mem, int normals_kernel_size) {
+    if (!b) return ICP_ERR_INVALID_ARGUMENT;
+    if (!rel_poses) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched projective map update: rel_poses is required");
+    DeviceGuard device_guard(b->device);
+    const int count = (int)b->members.size();
+    icp_ctx* const* ctxs = b->members.data();
+    icp_ctx* first = ctxs[0];
+    bool any_insert = false;
+    for (int i = 0; i < count; ++i) any_insert = any_insert || (vmaps && vmaps[i]);
+    if (any_insert && (normals_kernel_size < 1 || normals_kernel_size > 15 || !(normals_kernel_size & 1)))
+        return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "normals_kernel_size must be odd, 1..15");
+    // ---- every member is checked before any member changes
+    int rc = pmap_batch_check(b, "batched projective map update");
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i) {
+        const char* why = nullptr;
+        if ((rc = pmap_window_check(ctxs[i], rel_poses + 16 * i, vmaps && vmaps[i], &why)))
+            return batch_fail(b, rc, "batched projective map update, member " + std::to_string(i) + ": " + why);
+    }
+    // ---- buffers: the new vertex maps on the device, the slot storage (kept), the model layers of the new windows
+    const size_t bytes = (size_t)first->cfg.height * first->cfg.width * 12;
+    const float* in[ICP_BATCH_MAX_SEQUENCES] = {};
+    int slots[ICP_BATCH_MAX_SEQUENCES];
+    size_t pairs = 0;
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        if ((rc = ensure_state(ctx))) return batch_fail(b, rc, ctx->error);
+        slots[i] = -1;
+        if (vmaps && vmaps[i]) {
+            const void* p;
+            if ((rc = import_buffer(ctx, vmaps[i], bytes, mem, ctx->stage_in, &p)) || (rc = pmap_reserve_store(ctx)))
+                return batch_fail(b, rc, ctx->error);
+            in[i] = (const float*)p;
+            slots[i] = pmap_free_slot(ctx);
+            if (slots[i] < 0) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "no free projective-map slot");
+        }
+        // the window after pmap_window_step: + the new map, - the oldest beyond local_map_size (never for the first map)
+        int k = (int)ctx->pm_slots.size() + (slots[i] >= 0 ? 1 : 0);
+        if (!ctx->pm_slots.empty() && k > ctx->cfg.local_map_size) k -= 1;
+        pairs += (size_t)k;
+    }
+    const size_t pad = 256;
+    const size_t ins_bytes = ((pmap_insert_desc_bytes() * (size_t)count + pad - 1) / pad) * pad;
+    const size_t need = ins_bytes + pmap_pair_desc_bytes() * (pairs > 0 ? pairs : 1);
+    int slot = 0;
+    if ((rc = table_slot_take(b, need, &slot))) return batch_fail(b, rc, first->error);
+    char* host = b->host[slot];
+    // ---- the windows (host only, nothing fails from here on but the HIP calls), the descriptors
+    int n_ins = 0, n_pairs = 0;
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        if (slots[i] >= 0) pmap_insert_desc(ctx, slots[i], in[i], normals_kernel_size, host + pmap_insert_desc_bytes() * n_ins++);
+        pmap_window_step(ctx, rel_poses + 16 * i, slots[i]);
+    }
+    // a member whose window has moved but whose model never reached the stream reports an empty map until its next update
+    auto invalidate = [&]() {
+        for (int i = 0; i < count; ++i) {
+            ctxs[i]->pm_slots.clear();
+            ctxs[i]->pm_poses.clear();
+        }
+    };
+    for (int i = 0; i < count; ++i) {
+        int k = 0;
+        if (n_pairs + ctxs[i]->pm_slots.size() > pairs) {  // (cannot happen: the count above is the window step's)
+            invalidate();
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "internal: projective window larger than counted");
+        }
+        if ((rc = pmap_pair_descs(ctxs[i], host + ins_bytes + pmap_pair_desc_bytes() * n_pairs, &k))) {
+            invalidate();
+            return batch_fail(b, rc, ctxs[i]->error);
+        }
+        n_pairs += k;
+    }
+    // ---- one copy, then the launches: the insertions, the clear, the projection and the resolve of every (member, slot)
+    const char* dev = b->dev[slot].as<char>();
+    rc = batch_hip(b, first, hipMemcpyAsync(b->dev[slot].ptr, host, need, hipMemcpyHostToDevice, first->stream),
+                   "hipMemcpyAsync(descriptors)");
+    if (!rc) rc = batch_hip(b, first, hipEventRecord(b->copied[slot], first->stream), "hipEventRecord(copied)");
+    if (!rc && (rc = pmap_launch_update_batch(first, dev, n_ins, dev + ins_bytes, n_pairs))) batch_fail(b, rc, first->error);
+    if (rc) {
+        invalidate();
+        return rc;
+    }
+    if (any_insert && mem == ICP_MEM_HOST) ICP_HIP(first, hipStreamSynchronize(first->stream));
     return ICP_OK;
 }
 

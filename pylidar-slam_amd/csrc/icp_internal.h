@@ -606,6 +606,7 @@ struct icp_ctx {
     std::vector<int> pm_slots;                 // storage slot of every kept map, oldest first
     struct PmPose { float m[16]; };
     std::vector<PmPose> pm_poses;              // pose of every kept map's frame in the current frame
+    bool pm_have_pose = false;                 // the state holds the final pose of a registration against this map
     icp::Profile prof;
 };
 
@@ -717,10 +718,23 @@ int kitti_correct_device(icp_ctx* ctx, const float* scan_dev, int64_t n, int str
 int normal_map_device(icp_ctx* ctx, const float* vmap_dev, int ks, float* nmap_dev);
 int neighbors_device(icp_ctx* ctx, const float* tgt, const float* ref, const float* fld, int k_maps, int c_fld,
                      float* nb_out, float* fld_out);
+int pmap_reserve_store(icp_ctx* ctx);
 int pmap_store_slot(icp_ctx* ctx, int slot, const float* vmap_dev, const float* nmap_dev);
 int pmap_build(icp_ctx* ctx);
 int pmap_iterate(icp_ctx* ctx, int* blocks_out);
 int pmap_associate(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* rows9_dev, int* flags_dev);
+// ... B maps per launch (icp_batch_pmap_*, api.hip): descriptors filled on the host, one table copy, then the launches —
+// registration: pmap_launch_begin_batch (targets, states, z-buffers), per iteration pmap_launch_iteration_batch (projection
+// + association + partial rows) and launch_sum_solve_batch; update: pmap_launch_update_batch (insertions, model rebuild)
+size_t pmap_reg_desc_bytes();
+size_t pmap_insert_desc_bytes();
+size_t pmap_pair_desc_bytes();
+int pmap_register_desc(icp_ctx* ctx, void* out, int* rows_out);
+int pmap_launch_begin_batch(icp_ctx* first, const PackDesc* packs_dev, const void* table_dev, int count, int max_n);
+int pmap_launch_iteration_batch(icp_ctx* first, const void* table_dev, int count, int max_n);
+void pmap_insert_desc(icp_ctx* ctx, int slot, const float* vmap_dev, int ks, void* out);
+int pmap_pair_descs(icp_ctx* ctx, void* out, int* count_out);
+int pmap_launch_update_batch(icp_ctx* first, const void* ins_dev, int n_ins, const void* pairs_dev, int n_pairs);
 
 // ---- grid_sample.hip
 int voxel_hash_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, double voxel, long long* voxels_dev,

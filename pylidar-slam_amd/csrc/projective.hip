@@ -29,13 +29,15 @@ struct PoseArg {
 // ---------------------------------------------------------------------------------------------------------------------
 // normal map
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void k_normal_map(const float* __restrict__ vmap, int h, int w, int ks, float* __restrict__ nmap) {
+// the normal of pixel p (k_normal_map; k_pm_insert_batch fuses it with k_pm_store)
+__device__ __forceinline__ void normal_at(const float* __restrict__ vmap, int h, int w, int ks, int p, float& nx, float& ny,
+                                          float& nz) {
     const int npix = h * w;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
     const int y = p / w, x = p % w, r = ks / 2;
     const float vx = vmap[p], vy = vmap[npix + p], vz = vmap[2 * npix + p];
-    float nx = 0.f, ny = 0.f, nz = 0.f;
+    nx = 0.f;
+    ny = 0.f;
+    nz = 0.f;
     // mask_null: norm == 0 (geometry.py:279)
     if (!(vx == 0.f && vy == 0.f && vz == 0.f)) {
         double s0 = 0, s1 = 0, s2 = 0, a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
@@ -75,6 +77,14 @@ __global__ void k_normal_map(const float* __restrict__ vmap, int h, int w, int k
             }
         }
     }
+}
+
+__global__ void k_normal_map(const float* __restrict__ vmap, int h, int w, int ks, float* __restrict__ nmap) {
+    const int npix = h * w;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    float nx, ny, nz;
+    normal_at(vmap, h, w, ks, p, nx, ny, nz);
     nmap[p] = nx;
     nmap[npix + p] = ny;
     nmap[2 * npix + p] = nz;
@@ -166,10 +176,9 @@ __global__ void k_zclear(unsigned long long* __restrict__ z, long long n) {
     if (i < n) z[i] = ~0ull;
 }
 
-// one slot: transform by its pose, project, z-buffer
-__global__ void k_pm_project(const float4* __restrict__ v4, int npix, PoseArg T, ProjArg pp,
-                             unsigned long long* __restrict__ zbuf) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+// one slot: transform by its pose, project, z-buffer (bodies shared with the batched kernels below)
+__device__ __forceinline__ void pm_project_body(const float4* __restrict__ v4, int npix, const PoseArg& T,
+                                                const ProjArg& pp, unsigned long long* __restrict__ zbuf, int i) {
     if (i >= npix) return;
     const float4 v = v4[i];
     if (v.w == 0.f) return;  // model_points *= mask (local_map.py:192-193): null points project nowhere
@@ -182,10 +191,14 @@ __global__ void k_pm_project(const float4* __restrict__ v4, int npix, PoseArg T,
     atomicMin(&zbuf[pix], ((unsigned long long)__float_as_uint(r) << 32) | (unsigned long long)(~(unsigned)i));
 }
 
-__global__ void k_pm_resolve(const float4* __restrict__ v4, const float4* __restrict__ n4, int npix, PoseArg T,
-                             const unsigned long long* __restrict__ zbuf, float4* __restrict__ mv,
-                             float4* __restrict__ mn) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void k_pm_project(const float4* __restrict__ v4, int npix, PoseArg T, ProjArg pp,
+                             unsigned long long* __restrict__ zbuf) {
+    pm_project_body(v4, npix, T, pp, zbuf, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__device__ __forceinline__ void pm_resolve_body(const float4* __restrict__ v4, const float4* __restrict__ n4, int npix,
+                                                const PoseArg& T, const unsigned long long* __restrict__ zbuf,
+                                                float4* __restrict__ mv, float4* __restrict__ mn, int p) {
     if (p >= npix) return;
     const unsigned long long k = zbuf[p];
     float4 ov = make_float4(0.f, 0.f, 0.f, 0.f), on = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -204,11 +217,18 @@ __global__ void k_pm_resolve(const float4* __restrict__ v4, const float4* __rest
     mn[p] = on;
 }
 
+__global__ void k_pm_resolve(const float4* __restrict__ v4, const float4* __restrict__ n4, int npix, PoseArg T,
+                             const unsigned long long* __restrict__ zbuf, float4* __restrict__ mv,
+                             float4* __restrict__ mn) {
+    pm_resolve_body(v4, n4, npix, T, zbuf, mv, mn, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // per-iteration kernels
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void k_pm_project_targets(const float4* __restrict__ tgt, int n, int mode, const RegState* __restrict__ st,
-                                     ProjArg pp, unsigned long long* __restrict__ zbuf) {
+__device__ __forceinline__ void pm_project_targets_body(const float4* __restrict__ tgt, int n, int mode,
+                                                        const RegState* __restrict__ st, const ProjArg& pp,
+                                                        unsigned long long* __restrict__ zbuf) {
     if (st->done) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -225,13 +245,20 @@ __global__ void k_pm_project_targets(const float4* __restrict__ tgt, int n, int 
     atomicMin(&zbuf[pix], ((unsigned long long)__float_as_uint(r) << 32) | (unsigned long long)(~(unsigned)i));
 }
 
+__global__ void k_pm_project_targets(const float4* __restrict__ tgt, int n, int mode, const RegState* __restrict__ st,
+                                     ProjArg pp, unsigned long long* __restrict__ zbuf) {
+    pm_project_targets_body(tgt, n, mode, st, pp, zbuf);
+}
+
 static constexpr int PM_THREADS = 256;
 
-__global__ __launch_bounds__(PM_THREADS) void k_pm_iterate(const float4* __restrict__ tgt, int npix, int k_maps,
-                                                           const unsigned long long* __restrict__ zbuf,
-                                                           const float4* __restrict__ mv, const float4* __restrict__ mn,
-                                                           const RegState* __restrict__ st, AlignParams ap,
-                                                           double* __restrict__ partials) {
+// CLEAR (the batched kernel): every z-buffer word read goes back to ~0 (through the same pointer), so the next iteration's
+// projection needs no clearing launch in front of it
+template <bool CLEAR>
+__device__ __forceinline__ void pm_iterate_body(const float4* __restrict__ tgt, int npix, int k_maps,
+                                                const unsigned long long* __restrict__ zbuf, const float4* __restrict__ mv,
+                                                const float4* __restrict__ mn, const RegState* __restrict__ st,
+                                                const AlignParams& ap, double* __restrict__ partials) {
     __shared__ float rowbuf[PM_THREADS][9];
     __shared__ double part[8][NEQ];
     if (st->done) return;
@@ -241,6 +268,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_pm_iterate(const float4* __restr
     for (int k = 0; k < 9; ++k) row[k] = 0.f;
     if (p < npix) {
         const unsigned long long key = zbuf[p];
+        if (CLEAR && key != ~0ull) const_cast<unsigned long long*>(zbuf)[p] = ~0ull;
         if (key != ~0ull) {  // a target point landed here (mask_not_null(new_points), local_map.py:222)
             const int i = (int)(~(unsigned)(key & 0xffffffffull));
             const float4 t = tgt[i];
@@ -295,6 +323,14 @@ __global__ __launch_bounds__(PM_THREADS) void k_pm_iterate(const float4* __restr
     }
 }
 
+__global__ __launch_bounds__(PM_THREADS) void k_pm_iterate(const float4* __restrict__ tgt, int npix, int k_maps,
+                                                           const unsigned long long* __restrict__ zbuf,
+                                                           const float4* __restrict__ mv, const float4* __restrict__ mn,
+                                                           const RegState* __restrict__ st, AlignParams ap,
+                                                           double* __restrict__ partials) {
+    pm_iterate_body<false>(tgt, npix, k_maps, zbuf, mv, mn, st, ap, partials);
+}
+
 // gather of the per-pixel association for the LocalMap.nearest_neighbor_search seam (local_map.py:205-235):
 // planar neighbour points / normals / target points per pixel + validity flag
 __global__ void k_pm_assoc(const float* __restrict__ tgt_xyz, int npix, int k_maps,
@@ -347,11 +383,19 @@ static ProjArg proj_arg(const icp_ctx* ctx) {
 }
 
 // ---- host side of the map --------------------------------------------------------------------------------------------
-int pmap_store_slot(icp_ctx* ctx, int slot, const float* vmap_dev, const float* nmap_dev) {
+// the storage of local_map_size + 1 slots (the stored maps are kept)
+int pmap_reserve_store(icp_ctx* ctx) {
     const int npix = ctx->cfg.height * ctx->cfg.width;
     const size_t cap = (size_t)(ctx->cfg.local_map_size + 1);
     ICP_HIP(ctx, ctx->pm_v.reserve(cap * npix * sizeof(float4), true, ctx->stream));
     ICP_HIP(ctx, ctx->pm_n.reserve(cap * npix * sizeof(float4), true, ctx->stream));
+    return ICP_OK;
+}
+
+int pmap_store_slot(icp_ctx* ctx, int slot, const float* vmap_dev, const float* nmap_dev) {
+    const int npix = ctx->cfg.height * ctx->cfg.width;
+    const int rc = pmap_reserve_store(ctx);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_pm_store, dim3((npix + 255) / 256), dim3(256), 0, ctx->stream, vmap_dev, nmap_dev, npix,
                        ctx->pm_v.as<float4>() + (size_t)slot * npix, ctx->pm_n.as<float4>() + (size_t)slot * npix);
     ICP_HIP(ctx, hipGetLastError());
@@ -418,6 +462,193 @@ int pmap_associate(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* rows9_d
                        ctx->zbuf.as<unsigned long long>(), ctx->pm_mv.as<float4>(), ctx->pm_mn.as<float4>(), rows9_dev,
                        flags_dev);
     ICP_HIP(ctx, hipGetLastError());
+    return ICP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// B maps per launch (icp_batch_pmap_register_launch / icp_batch_pmap_update, api.hip).  Every kernel reads its members'
+// arguments BY VALUE from a descriptor table in device memory (blockIdx.y = the member, or the (member, slot) pair) and
+// runs the body of the single kernel above: per member the same operations in the same order, the same bits.
+// ---------------------------------------------------------------------------------------------------------------------
+struct PmRegDesc {  // one member's registration
+    const float4* tgt;
+    const float4* mv;
+    const float4* mn;
+    RegState* st;
+    unsigned long long* zbuf;  // [H*W]
+    double* partials;          // [H*W / PM_THREADS][NEQ]
+    AlignParams ap;
+    int n, mode, k_maps, pad;
+};
+
+struct PmInsertDesc {  // one member's new vertex map -> its free slot
+    const float* vmap;  // [3,H,W]
+    float4* v4;
+    float4* n4;
+    int ks, pad[3];
+};
+
+struct PmPairDesc {  // one stored map of one member: its slot, its pose in the current frame, its model layer
+    const float4* v4;
+    const float4* n4;
+    unsigned long long* z;
+    float4* mv;
+    float4* mn;
+    PoseArg T;
+};
+
+// the registration's first launch: k_pack_targets_batch (targets + state) and the z-buffer clear of every member
+__global__ void k_pm_begin_batch(const PackDesc* __restrict__ packs, const PmRegDesc* __restrict__ table, int npix) {
+    const PackDesc& d = packs[blockIdx.y];  // (by reference, as k_pack_targets_batch: init.m is indexed by lane)
+    unsigned long long* z = table[blockIdx.y].zbuf;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d.st && i < 64) state_init_wave(d.st, d.init.m, d.keep_pose, d.box, d.gen, d.hist, i);
+    if (i < npix) z[i] = ~0ull;
+    if (i >= d.n) return;
+    d.out[i] = make_float4(d.xyz[3 * i], d.xyz[3 * i + 1], d.xyz[3 * i + 2], __int_as_float(i));
+}
+
+__global__ void k_pm_project_targets_batch(const PmRegDesc* __restrict__ table, ProjArg pp) {
+    const PmRegDesc d = table[blockIdx.y];
+    pm_project_targets_body(d.tgt, d.n, d.mode, d.st, pp, d.zbuf);
+}
+
+__global__ __launch_bounds__(PM_THREADS) void k_pm_iterate_batch(const PmRegDesc* __restrict__ table, int npix) {
+    const PmRegDesc d = table[blockIdx.y];
+    pm_iterate_body<true>(d.tgt, npix, d.k_maps, d.zbuf, d.mv, d.mn, d.st, d.ap, d.partials);
+}
+
+// k_normal_map + k_pm_store in one pass
+__global__ void k_pm_insert_batch(const PmInsertDesc* __restrict__ table, int h, int w) {
+    const PmInsertDesc d = table[blockIdx.y];
+    const int npix = h * w;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    float nx, ny, nz;
+    normal_at(d.vmap, h, w, d.ks, p, nx, ny, nz);
+    const float x = d.vmap[p], y = d.vmap[npix + p], z = d.vmap[2 * npix + p];
+    const bool ok = fmaxf(fmaxf(fabsf(x), fabsf(y)), fabsf(z)) > 0.f;  // mask_not_null (local_map.py:141)
+    d.v4[p] = make_float4(x, y, z, ok ? 1.f : 0.f);
+    d.n4[p] = make_float4(nx, ny, nz, 0.f);
+}
+
+__global__ void k_pm_zclear_batch(const PmPairDesc* __restrict__ table, int npix) {
+    unsigned long long* z = table[blockIdx.y].z;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < npix) z[p] = ~0ull;
+}
+
+__global__ void k_pm_project_batch(const PmPairDesc* __restrict__ table, int npix, ProjArg pp) {
+    const PmPairDesc d = table[blockIdx.y];
+    pm_project_body(d.v4, npix, d.T, pp, d.z, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ void k_pm_resolve_batch(const PmPairDesc* __restrict__ table, int npix) {
+    const PmPairDesc d = table[blockIdx.y];
+    pm_resolve_body(d.v4, d.n4, npix, d.T, d.z, d.mv, d.mn, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+size_t pmap_reg_desc_bytes() { return sizeof(PmRegDesc); }
+size_t pmap_insert_desc_bytes() { return sizeof(PmInsertDesc); }
+size_t pmap_pair_desc_bytes() { return sizeof(PmPairDesc); }
+
+// a member's registration descriptor (its targets, state and result slot prepared); *rows_out = partial rows per iteration
+int pmap_register_desc(icp_ctx* ctx, void* out, int* rows_out) {
+    const int npix = ctx->cfg.height * ctx->cfg.width;
+    const int blocks = (npix + PM_THREADS - 1) / PM_THREADS;
+    ICP_HIP(ctx, ctx->zbuf.reserve((size_t)npix * sizeof(unsigned long long)));
+    ICP_HIP(ctx, ctx->partials.reserve((size_t)blocks * NEQ * sizeof(double)));
+    ctx->zbuf_clean = nullptr;  // (as pmap_iterate: the next icp_project on this context clears first)
+    PmRegDesc d;
+    memset(&d, 0, sizeof(d));
+    d.tgt = ctx->tgt4.as<float4>();
+    d.mv = ctx->pm_mv.as<float4>();
+    d.mn = ctx->pm_mn.as<float4>();
+    d.st = reg_state(ctx);
+    d.zbuf = ctx->zbuf.as<unsigned long long>();
+    d.partials = ctx->partials.as<double>();
+    d.ap = make_align_params(ctx);
+    d.n = (int)ctx->tgt_n;
+    d.mode = ctx->tgt_mode;
+    d.k_maps = (int)ctx->pm_slots.size();
+    memcpy(out, &d, sizeof(d));
+    *rows_out = blocks;
+    return ICP_OK;
+}
+
+int pmap_launch_begin_batch(icp_ctx* first, const PackDesc* packs_dev, const void* table_dev, int count, int max_n) {
+    const int npix = first->cfg.height * first->cfg.width;
+    const int n = max_n > npix ? max_n : npix;
+    hipLaunchKernelGGL(k_pm_begin_batch, dim3((unsigned)((n + 255) / 256), count), dim3(256), 0, first->stream, packs_dev,
+                       reinterpret_cast<const PmRegDesc*>(table_dev), npix);
+    ICP_HIP(first, hipGetLastError());
+    return ICP_OK;
+}
+
+// one ICP iteration of every member, its summing / solving launch left to the caller: project the targets, associate
+int pmap_launch_iteration_batch(icp_ctx* first, const void* table_dev, int count, int max_n) {
+    const int npix = first->cfg.height * first->cfg.width;
+    const PmRegDesc* table = reinterpret_cast<const PmRegDesc*>(table_dev);
+    if (max_n > 0)
+        hipLaunchKernelGGL(k_pm_project_targets_batch, dim3((unsigned)((max_n + 255) / 256), count), dim3(256), 0,
+                           first->stream, table, proj_arg(first));
+    hipLaunchKernelGGL(k_pm_iterate_batch, dim3((npix + PM_THREADS - 1) / PM_THREADS, count), dim3(PM_THREADS), 0,
+                       first->stream, table, npix);
+    ICP_HIP(first, hipGetLastError());
+    return ICP_OK;
+}
+
+// a member's new vertex map (device, [3,H,W]) into `slot` (pmap_reserve_store first)
+void pmap_insert_desc(icp_ctx* ctx, int slot, const float* vmap_dev, int ks, void* out) {
+    const size_t npix = (size_t)ctx->cfg.height * ctx->cfg.width;
+    PmInsertDesc d;
+    memset(&d, 0, sizeof(d));
+    d.vmap = vmap_dev;
+    d.v4 = ctx->pm_v.as<float4>() + (size_t)slot * npix;
+    d.n4 = ctx->pm_n.as<float4>() + (size_t)slot * npix;
+    d.ks = ks;
+    memcpy(out, &d, sizeof(d));
+}
+
+// the model buffers of the member's window and one PmPairDesc per kept map (as pmap_build): the number written
+int pmap_pair_descs(icp_ctx* ctx, void* out, int* count_out) {
+    const int npix = ctx->cfg.height * ctx->cfg.width;
+    const int k_maps = (int)ctx->pm_slots.size();
+    *count_out = 0;
+    if (k_maps == 0) return ICP_OK;
+    ICP_HIP(ctx, ctx->pm_mv.reserve((size_t)k_maps * npix * sizeof(float4)));
+    ICP_HIP(ctx, ctx->pm_mn.reserve((size_t)k_maps * npix * sizeof(float4)));
+    ICP_HIP(ctx, ctx->pm_z.reserve((size_t)k_maps * npix * sizeof(unsigned long long)));
+    PmPairDesc* t = reinterpret_cast<PmPairDesc*>(out);
+    for (int k = 0; k < k_maps; ++k) {
+        PmPairDesc d;
+        memset(&d, 0, sizeof(d));
+        d.v4 = ctx->pm_v.as<float4>() + (size_t)ctx->pm_slots[k] * npix;
+        d.n4 = ctx->pm_n.as<float4>() + (size_t)ctx->pm_slots[k] * npix;
+        d.z = ctx->pm_z.as<unsigned long long>() + (size_t)k * npix;
+        d.mv = ctx->pm_mv.as<float4>() + (size_t)k * npix;
+        d.mn = ctx->pm_mn.as<float4>() + (size_t)k * npix;
+        memcpy(d.T.m, ctx->pm_poses[k].m, sizeof(d.T.m));
+        memcpy(t + k, &d, sizeof(d));
+    }
+    *count_out = k_maps;
+    return ICP_OK;
+}
+
+// the map update of every member: the insertions, then the model rebuild of every (member, slot) pair — four launches
+int pmap_launch_update_batch(icp_ctx* first, const void* ins_dev, int n_ins, const void* pairs_dev, int n_pairs) {
+    const int h = first->cfg.height, w = first->cfg.width, npix = h * w;
+    const unsigned nb = (npix + 255) / 256;
+    if (n_ins > 0)
+        hipLaunchKernelGGL(k_pm_insert_batch, dim3(nb, n_ins), dim3(256), 0, first->stream,
+                           reinterpret_cast<const PmInsertDesc*>(ins_dev), h, w);
+    if (n_pairs > 0) {
+        const PmPairDesc* pairs = reinterpret_cast<const PmPairDesc*>(pairs_dev);
+        hipLaunchKernelGGL(k_pm_zclear_batch, dim3(nb, n_pairs), dim3(256), 0, first->stream, pairs, npix);
+        hipLaunchKernelGGL(k_pm_project_batch, dim3(nb, n_pairs), dim3(256), 0, first->stream, pairs, npix, proj_arg(first));
+        hipLaunchKernelGGL(k_pm_resolve_batch, dim3(nb, n_pairs), dim3(256), 0, first->stream, pairs, npix);
+    }
+    ICP_HIP(first, hipGetLastError());
     return ICP_OK;
 }
 

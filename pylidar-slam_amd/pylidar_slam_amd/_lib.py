@@ -128,6 +128,8 @@ EXPORTED_SYMBOLS = {
     "icp_batch_project": (_INT, [_P, _P, _P, _P]),
     "icp_batch_map_update": (_INT, [_P]),
     "icp_batch_map_update_staged": (_INT, [_P, _P, _P, _P]),
+    "icp_batch_pmap_register_launch": (_INT, [_P, _P, _P, _INT, _INT, _P, _INT]),
+    "icp_batch_pmap_update": (_INT, [_P, _P, _P, _INT, _INT]),
     "icp_batch_register_end": (_INT, [_P, _P, _P, _P]),
     "icp_normal_equations_ptr": (_P, [_P]),
     "icp_set_normal_equations_buffer": (_INT, [_P, _P]),

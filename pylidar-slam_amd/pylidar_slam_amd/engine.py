@@ -793,6 +793,15 @@ class IcpBatch:
         """`scans[b]`: member b's scan ([n_b, 3] float32; all cuda tensors or all host arrays).  `init_poses`: a list of
         4x4 matrices (None entries: identity), None (identity for all) or "last" (every member starts from the device-resident
         pose of its previous registration: constant-velocity initialisation without a host round trip)."""
+        self._launch(self._lib.icp_batch_register_launch, scans, init_poses, skip_null)
+
+    def pmap_register_launch(self, scans, init_poses=None, skip_null: bool = False):
+        """`IcpContext.pmap_register` on every member against its projective map (icp_batch_pmap_register_launch): every
+        iteration of all members enqueued, three launches per iteration; `register_end` collects the results.  `scans`,
+        `init_poses` and `skip_null` as for `register_launch`."""
+        self._launch(self._lib.icp_batch_pmap_register_launch, scans, init_poses, skip_null)
+
+    def _launch(self, fn, scans, init_poses, skip_null):
         if len(scans) != len(self.contexts):
             raise AssertionError(f"expected {len(self.contexts)} scans, got {len(scans)}")
         if _on_device(*scans):
@@ -814,7 +823,7 @@ class IcpBatch:
         if isinstance(init_poses, str):
             if init_poses != "last":
                 raise AssertionError(f"unknown initial pose {init_poses!r}")
-            self._check(self._lib.icp_batch_register_launch(self._h, xyz, n, mem, mode, None, 1))
+            self._check(fn(self._h, xyz, n, mem, mode, None, 1))
             return
         init = None
         if init_poses is not None:
@@ -823,8 +832,7 @@ class IcpBatch:
             if flat.shape[0] != len(self.contexts):
                 raise AssertionError("one initial pose per member")
             init = np.ascontiguousarray(flat)
-        self._check(self._lib.icp_batch_register_launch(self._h, xyz, n, mem, mode,
-                                                        init.ctypes.data if init is not None else None, 0))
+        self._check(fn(self._h, xyz, n, mem, mode, init.ctypes.data if init is not None else None, 0))
 
     def project(self, scans, outs):
         """`IcpContext.project(scans[b], out=outs[b])` for every member in two launches (cuda tensors: [n_b, 3] float32 scans,
@@ -873,6 +881,31 @@ class IcpBatch:
         ins = (C.c_int64 * b)()
         self._check(self._lib.icp_batch_map_update_staged(self._h, rel.ctypes.data if rel is not None else None, flags, ins))
         return [int(v) for v in ins]
+
+    def pmap_update(self, rel_poses, vmaps, normals_kernel_size: int = 5):
+        """`IcpContext.pmap_update(rel_poses[b], vmaps[b], normals_kernel_size)` on every member in four launches
+        (icp_batch_pmap_update): `vmaps[b]` a [3,H,W] vertex map (all cuda tensors or all host arrays) to insert, or None for
+        a pose-only update; `vmaps` None: pose-only for every member."""
+        b = len(self.contexts)
+        if len(rel_poses) != b or (vmaps is not None and len(vmaps) != b):
+            raise AssertionError(f"expected {b} relative poses and vertex maps")
+        rel = np.ascontiguousarray(np.stack([np.asarray(m, dtype=np.float32).reshape(16) for m in rel_poses]))
+        ptrs, keep, mems = [None] * b, [], set()
+        for i, (c, v) in enumerate(zip(self.contexts, vmaps if vmaps is not None else [None] * b)):
+            if v is None:
+                continue
+            p, mem, k = c._planar(v)
+            ptrs[i] = p
+            keep.append(k)
+            mems.add(mem)
+        if len(mems) > 1:
+            raise AssertionError("the vertex maps of a batch must live in one memory space")
+        mem = mems.pop() if mems else MEM_DEVICE
+        if mem == MEM_DEVICE:
+            self.use_torch_stream()
+        vm = (C.c_void_p * b)(*ptrs)
+        self._keep_vmaps = keep  # (alive until the next update: the copies _planar made are read by the enqueued launches)
+        self._check(self._lib.icp_batch_pmap_update(self._h, rel.ctypes.data, vm, mem, int(normals_kernel_size)))
 
     def register_end(self):
         """One wait for all members; a list of `RegisterResult`s (raises what the first failing member would raise)."""

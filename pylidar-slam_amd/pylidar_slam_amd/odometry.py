@@ -1070,22 +1070,27 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
 
 # ----------------------------------------------------------------------------------------------------------------------
 class MI355XICPFrameToModelBatch:
-    """B independent sequences of `MI355XICPFrameToModel` (kd-tree style map, point-to-plane) advanced together: one call
-    takes the next frame of every sequence, registers all of them with one launch per ICP iteration (`IcpBatch`) and
-    updates all B maps — key-frame insertion, eviction, grid rebuild and eager normals — with one `map_update_staged`.
-    Per sequence the same poses, iteration counts, maps and normals, bit for bit, as `MI355XICPFrameToModel` on the same
-    frames (ICPFrameToModel.do_process_next_frame, slam/odometry/icp_odometry.py:157-246; __update_map :360-380).
+    """B independent sequences of `MI355XICPFrameToModel` (point-to-plane) advanced together: one call takes the next
+    frame of every sequence, registers all of them together (`IcpBatch`) and updates all B local maps with one call.
+    Per sequence the same poses, iteration counts, losses, steps and maps, bit for bit, as `MI355XICPFrameToModel` on the
+    same frames (ICPFrameToModel.do_process_next_frame, slam/odometry/icp_odometry.py:157-246; __update_map :360-380).
 
-    Input: torch tensors (the device-resident preprocessing of config/slam/preprocessing/grid_sample_mi355x.yaml).
-    Per member still: the projection, the staging of the frame's rows and the frame-0 insertion of the vertex map."""
+    kd-tree style map (kdtree_local_map / hashgrid_local_map): one launch per ICP iteration for all B registrations and
+    one `map_update_staged` — key-frame insertion, eviction, grid rebuild and eager normals.  Per member still: the
+    projection, the staging of the frame's rows and the frame-0 insertion of the vertex map.
+
+    Projective map (projective_local_map, local_map.py:91-240): frame 0 is one batched insertion; every later frame is one
+    `pmap_register_launch` (three launches per ICP iteration for all B, every iteration enqueued) and one `pmap_update`
+    (four launches: the vertex maps of the members that take a key frame, the model rebuild of every member).  Per member
+    still: `_read_input` (the projection of an [N,3] frame).
+
+    Input: torch tensors (device-resident preprocessing, or [3,H,W] / [1,3,H,W] vertex maps)."""
 
     def __init__(self, config: MI355XICPConfig, count: int, projector=None, device=None, **kwargs):
         assert_debug(int(count) >= 1, "a batch needs at least one sequence")
         self.members = [MI355XICPFrameToModel(config, projector=projector, device=device, **kwargs) for _ in range(int(count))]
         m0 = self.members[0]
         self.config = m0.config
-        assert_debug(not m0._projective, "MI355XICPFrameToModelBatch batches the kd-tree style local map only "
-                                         "(kdtree_local_map / hashgrid_local_map), not the projective map")
         assert_debug(not m0._point_to_point, "MI355XICPFrameToModelBatch batches the point-to-plane alignment only "
                                              "(point_to_plane_gauss_newton), not point-to-point")
         self.batch = IcpBatch([m.ctx for m in self.members])
@@ -1127,6 +1132,9 @@ class MI355XICPFrameToModelBatch:
         self.batch.use_torch_stream()
         for m, d in zip(members, data_dicts):
             m._read_input(d)  # the projection, per member
+        if members[0]._projective:
+            self._process_projective(data_dicts)
+            return
         if self._iter == 0:
             eye = np.eye(4, dtype=np.float32)
             for m in members:  # :176
@@ -1161,6 +1169,50 @@ class MI355XICPFrameToModelBatch:
             m.last_result = res
             if key_frame:
                 m.local_map._last_count = ins
+            m.relative_poses.append(res.pose[None].copy())
+            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
+            d[m.pointcloud_key()] = pc  # :243
+            d[m.relative_pose_key()] = res.pose.reshape(4, 4).copy()  # :244
+            m._iter += 1
+        self._iter += 1
+
+    def _process_projective(self, data_dicts):
+        """The projective-map frame of every member (MI355XICPFrameToModel.do_process_next_frame with `_projective`)."""
+        members = self.members
+        ks = members[0].local_map.normals_kernel_size
+        if self._iter == 0:  # :176 — every member's first vertex map, one batched insertion
+            eye = np.eye(4, dtype=np.float32)
+            self.batch.pmap_update([eye] * len(members), [m._tgt_vmap for m in members], ks)
+            for m in members:
+                m.local_map._last_vmap = m._tgt_vmap
+                m.relative_poses.append(eye[None])
+                m.absolute_poses.append(np.eye(4, dtype=np.float64))
+                m._iter += 1
+            self._iter += 1
+            return
+        inits = [m._initial_pose(d) for m, d in zip(members, data_dicts)]
+        sampled = [m.sample_points() for m in members]
+        assert_debug(len({s for _, s in sampled}) == 1,
+                     "the frames of one batched call must be all point clouds or all vertex maps")
+        want = ["distorted" not in d for d in data_dicts]
+        ready = [m._rows_event() if w else None for m, w in zip(members, want)]
+        self.batch.pmap_register_launch([t for t, _ in sampled], inits, skip_null=sampled[0][1])
+        pcs = [m._rows_to_host(r) if w else d["distorted"] for m, r, w, d in zip(members, ready, want, data_dicts)]
+        results = self.batch.register_end()  # raises before a map is touched (:286)
+        # the key-frame decisions, each with __update_map's own arithmetic (:360-380)
+        vmaps = []
+        for m, res in zip(members, results):
+            new_delta = (m._delta_since_map_update @ res.pose).astype(np.float32)
+            dp = from_pose_matrix(new_delta)
+            key_frame = bool(np.linalg.norm(dp[:3]) > m._register_threshold_trans or
+                             np.linalg.norm(dp[3:]) * 180 / np.pi > m._register_threshold_rot)
+            m._delta_since_map_update = np.eye(4, dtype=np.float32) if key_frame else new_delta
+            vmaps.append(m._tgt_vmap if key_frame else None)
+        self.batch.pmap_update([res.pose for res in results], vmaps, ks)
+        for m, res, d, pc, vm in zip(members, results, data_dicts, pcs, vmaps):
+            m.last_result = res
+            if vm is not None:
+                m.local_map._last_vmap = vm
             m.relative_poses.append(res.pose[None].copy())
             m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
             d[m.pointcloud_key()] = pc  # :243
