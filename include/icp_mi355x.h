@@ -516,7 +516,34 @@ int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
  *                              regular relative pose;
  *   icp_batch_register_end     icp_register_end for every member (results[b]; loss_per_iter_out / dx_per_iter_out:
  *                              count x max_num_alignments (x 6) entries or NULL): ONE wait for all of them.  Returns the
- *                              first member's non-zero status, every member's own in results[b].status. */
+ *                              first member's non-zero status, every member's own in results[b].status.
+ * The stage in front of them — every call below follows the same rules: DEVICE pointers only, everything enqueued on the
+ * batch's stream behind what each member already has there (iterations the batch or a member still holds back are enqueued
+ * first), every member checked before anything is enqueued (ICP_ERR_INVALID_ARGUMENT, nothing enqueued, no member changed,
+ * when a member is on another stream, is inside a registration — icp_register_begin .. icp_register_end — or its arguments
+ * are inconsistent), nothing read back:
+ *   icp_batch_preprocess       the reference's Preprocessing chain Distortion -> GridSample -> ToTensor(float32)
+ *                              (slam/preprocessing.py:144-191, :207-226, :101-126; the chain :269-290) for frames[b] of every
+ *                              member b, with the padded grid sample of icp_grid_sample_padded[_f64].  A frame with
+ *                              `timestamps` ([n] float64) is de-skewed by rel_pose (as icp_distort) into distorted_out ([n,3]
+ *                              float64, required exactly then) and sampled from those float64 rows; a frame without (NULL:
+ *                              Distortion's pass-through) is sampled from its float32 rows.  samples_out (optional): the n
+ *                              padded sample rows in the frame's element type (float64 when de-skewed, float32 otherwise) —
+ *                              the V samples by ascending voxel hash, NaN rows behind them; samples_f32_out (required when
+ *                              n > 0): the same rows cast to float32 ((float)x); indices_out (optional): [n] int64, -1 behind
+ *                              the samples; count_out (required): V, an int32 on the device.  Per member the same bits as
+ *                              icp_distort + icp_grid_sample_padded[_f64] + a float32 cast on that member alone.  Two launches
+ *                              de-skew the members that have timestamps, four sample every member (one per kernel kind for the
+ *                              whole batch); a frame of more than 262 144 points takes the single path in the same call;
+ *   icp_batch_project_rows     icp_project_rows (Projector.build_projection_map, slam/common/projection.py:331-418, as
+ *                              ICPFrameToModel._read_input calls it per frame, slam/odometry/icp_odometry.py:319-358) for every
+ *                              member in two launches: xyz[b] [n[b],3] -> vmap_out[b] [3,H,W] and rows_out[b] [H*W,3] (rows_out
+ *                              or rows_out[b] NULL: the vertex map only, as icp_batch_project);
+ *   icp_batch_stage            icp_map_stage_cloud (the frame's valid rows, compacted and counted in front of its registration,
+ *                              for the insertion of slam/odometry/icp_odometry.py:229-231) for every member in two launches:
+ *                              xyz[b] [n[b],3] (NULL when n[b] == 0), row_mode ICP_TARGETS_*; every member's count lands in its
+ *                              pinned word, its staged event is recorded: icp_batch_map_update_staged / icp_map_update_staged
+ *                              consume the staged clouds as after icp_map_stage_cloud. */
 #define ICP_BATCH_MAX_SEQUENCES 32
 typedef struct icp_batch icp_batch;
 int icp_batch_create(icp_ctx* const* ctxs, int32_t count, icp_batch** out);
@@ -534,6 +561,21 @@ int icp_batch_pmap_update(icp_batch* batch, const float* rel_poses, const float*
                           int normals_kernel_size);
 int icp_batch_register_end(icp_batch* batch, icp_register_result* results, double* loss_per_iter_out,
                            float* dx_per_iter_out);
+typedef struct icp_preprocess_frame {
+    const float* xyz;         /* [n,3] float32 */
+    int64_t n;
+    const double* timestamps; /* [n] float64, or NULL: no de-skew */
+    double rel_pose[16];      /* the initial motion estimate (read when timestamps is set) */
+    double* distorted_out;    /* [n,3] float64: required exactly when timestamps is set */
+    void* samples_out;        /* optional: [n,3] padded samples, float64 when de-skewed, float32 otherwise */
+    float* samples_f32_out;   /* [n,3] float32 copy of the padded samples (required when n > 0) */
+    int64_t* indices_out;     /* optional: [n] int64 */
+    int32_t* count_out;       /* required: V */
+} icp_preprocess_frame;
+int icp_batch_preprocess(icp_batch* batch, const icp_preprocess_frame* frames, double voxel_size);
+int icp_batch_project_rows(icp_batch* batch, const float* const* xyz, const int64_t* n, float* const* vmap_out,
+                           float* const* rows_out);
+int icp_batch_stage(icp_batch* batch, const float* const* xyz, const int64_t* n, int row_mode);
 
 /* ---- multi-GPU exchange inside the library ("one-shot P2P write+flag all-reduce") -----------------
  * The per-iteration exchange of the scan-sharded registration without leaving the library: after these three calls

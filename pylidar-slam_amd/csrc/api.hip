@@ -2296,6 +2296,124 @@ int icp_batch_project(icp_batch* b, const float* const* xyz, const int64_t* n, f
     return ICP_OK;
 }
 
+static int batch_hip(icp_batch* b, icp_ctx* ctx, hipError_t e, const char* what);
+
+// ---- the stage in front of a batched registration: preprocessing, projection, staging -----------------------------------
+// What each of these calls asks of its members before anything is enqueued: one stream, no registration in progress
+// (icp_register_begin .. icp_register_end).  `join`: the member's stream first waits for a map update running on the map
+// stream (as the single entry point the call replaces does).
+static int front_batch_check(icp_batch* b, const char* what, bool join) {
+    icp_ctx* first = b->members[0];
+    for (size_t i = 0; i < b->members.size(); ++i) {
+        icp_ctx* ctx = b->members[i];
+        if (join) { DeviceGuard join_map_stream(ctx); }
+        const std::string who = std::string(what) + ", member " + std::to_string(i) + ": ";
+        if (ctx->stream != first->stream)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "the members must enqueue on one stream (icp_batch_set_stream)");
+        if (ctx->in_registration) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "registration in progress");
+    }
+    return ICP_OK;
+}
+
+// ... then iterations the batch or a member still holds back go onto the stream first (stream order = call order)
+static int front_batch_flush(icp_batch* b) {
+    int rc = batch_flush(b);
+    if (rc) return rc;
+    for (icp_ctx* ctx : b->members)
+        if ((rc = continue_launch(ctx, -1)) || (rc = ensure_state(ctx))) return batch_fail(b, rc, ctx->error);
+    return ICP_OK;
+}
+
+// Distortion -> GridSample(padded) -> ToTensor(float32) (slam/preprocessing.py:144-191, :207-226, :101-126) for B frames
+int icp_batch_preprocess(icp_batch* b, const icp_preprocess_frame* frames, double voxel_size) {
+    if (!b) return ICP_ERR_INVALID_ARGUMENT;
+    if (!frames || !(voxel_size > 0))
+        return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched preprocessing: frames[] and a positive voxel size are required");
+    DeviceGuard device_guard(b->device);
+    const int count = (int)b->members.size();
+    for (int i = 0; i < count; ++i) {
+        const icp_preprocess_frame& f = frames[i];
+        const std::string who = "batched preprocessing, member " + std::to_string(i) + ": ";
+        if (f.n < 0 || f.n > INT32_MAX) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "invalid row count");
+        if (!f.count_out) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "count_out is required");
+        if (f.n > 0 && (!f.xyz || !f.samples_f32_out))
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "xyz and samples_f32_out are required");
+        if (f.n > 0 && f.timestamps && !f.distorted_out)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "a de-skewed frame needs distorted_out");
+        if (!f.timestamps && f.distorted_out)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "distorted_out without timestamps");
+    }
+    int rc = front_batch_check(b, "batched preprocessing", false);
+    if (rc || (rc = front_batch_flush(b))) return rc;
+    if ((rc = preprocess_batch_device(b->members.data(), count, frames, voxel_size))) {
+        for (icp_ctx* ctx : b->members)
+            if (!ctx->error.empty()) return batch_fail(b, rc, ctx->error);
+        return batch_fail(b, rc, "batched preprocessing: HIP error");
+    }
+    return ICP_OK;
+}
+
+// icp_project_rows (slam/common/projection.py:331-418; icp_odometry.py:319-358) for every member in two launches
+int icp_batch_project_rows(icp_batch* b, const float* const* xyz, const int64_t* n, float* const* vmap_out,
+                           float* const* rows_out) {
+    if (!b) return ICP_ERR_INVALID_ARGUMENT;
+    if (!xyz || !n || !vmap_out) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched projection: xyz[], n[] and vmap_out[] are required");
+    DeviceGuard device_guard(b->device);
+    const int count = (int)b->members.size();
+    for (int i = 0; i < count; ++i)
+        if (n[i] < 0 || n[i] > INT32_MAX || (n[i] > 0 && !xyz[i]) || !vmap_out[i])
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched projection, member " + std::to_string(i) +
+                                                               ": a device scan and a vertex map are required");
+    int rc = front_batch_check(b, "batched projection", false);
+    if (rc || (rc = front_batch_flush(b))) return rc;
+    if ((rc = project_batch_device(b->members.data(), count, xyz, n, vmap_out, rows_out))) return batch_fail(b, rc, b->members[0]->error);
+    return ICP_OK;
+}
+
+// icp_map_stage_cloud (the insertion of icp_odometry.py:229-231, prepared in front of the registration) for every member
+int icp_batch_stage(icp_batch* b, const float* const* xyz, const int64_t* n, int row_mode) {
+    if (!b) return ICP_ERR_INVALID_ARGUMENT;
+    if (!xyz || !n) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched staging: xyz[] and n[] are required");
+    DeviceGuard device_guard(b->device);
+    const int count = (int)b->members.size();
+    icp_ctx* const* ctxs = b->members.data();
+    for (int i = 0; i < count; ++i)
+        if (n[i] < 0 || (n[i] > 0 && !xyz[i]))
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched staging, member " + std::to_string(i) + ": a device cloud is required");
+    int rc = front_batch_check(b, "batched staging", true);
+    if (rc || (rc = front_batch_flush(b))) return rc;
+    int* mapped[ICP_BATCH_MAX_SEQUENCES] = {};
+    float* out[ICP_BATCH_MAX_SEQUENCES] = {};
+    for (int i = 0; i < count; ++i) {  // (as icp_map_stage_cloud, member by member)
+        icp_ctx* ctx = ctxs[i];
+        if (!ctx->staged_count_host &&
+            (rc = batch_hip(b, ctx, hipHostMalloc((void**)&ctx->staged_count_host, sizeof(int), hipHostMallocDefault), "hipHostMalloc")))
+            return rc;
+        if (!ctx->staged_event &&
+            (rc = batch_hip(b, ctx, hipEventCreateWithFlags(&ctx->staged_event, hipEventDisableTiming), "hipEventCreate")))
+            return rc;
+        // an earlier staged cloud that was never consumed: its count may still be in flight towards the pinned word
+        if (ctx->staged_rows >= 0 && (rc = batch_hip(b, ctx, hipEventSynchronize(ctx->staged_event), "hipEventSynchronize")))
+            return rc;
+        ctx->staged_rows = -1;
+        *ctx->staged_count_host = 0;
+        if (n[i] > 0) {
+            if ((rc = batch_hip(b, ctx, ctx->staged_xyz.reserve((size_t)n[i] * 12), "reserve(staged_xyz)")) ||
+                (rc = batch_hip(b, ctx, hipHostGetDevicePointer((void**)&mapped[i], ctx->staged_count_host, 0), "hipHostGetDevicePointer")))
+                return rc;
+            out[i] = ctx->staged_xyz.as<float>();
+        }
+    }
+    if ((rc = compact_valid_rows_batch(ctxs, count, xyz, n, row_mode == ICP_TARGETS_SKIP_NULL, out, mapped)))
+        return batch_fail(b, rc, ctxs[0]->error);
+    for (int i = 0; i < count; ++i) {
+        icp_ctx* ctx = ctxs[i];
+        if ((rc = batch_hip(b, ctx, hipEventRecord(ctx->staged_event, ctx->stream), "hipEventRecord(staged_event)"))) return rc;
+        ctx->staged_rows = n[i];
+    }
+    return ICP_OK;
+}
+
 // the next pinned slot of the map-update descriptors (and its device twin), free to be rewritten: its copy is three updates old
 static constexpr size_t GRID_SLOT_BYTES =
     sizeof(GridBuildDesc) * ICP_BATCH_MAX_SEQUENCES + sizeof(NormalsBatchDesc) * ICP_BATCH_MAX_SEQUENCES;

@@ -9,6 +9,7 @@
 //   hash   = 73856093 x + 19349669 y + 83492791 z                wrapping int64
 //   dedupe (hash -> smallest index) through a hash table, then sort the V distinct (hash, index) pairs by hash.
 // The sort of the V pairs is rocPRIM's device radix sort (a library primitive); everything else is hand-written.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string.h>
@@ -101,9 +102,10 @@ struct DedupeSlot {
 
 // + (padded outputs) the 0xFF bytes behind the samples — NaN points, index -1: the same launch writes them (two memset
 // launches less in front of every frame)
-__global__ void k_dedupe_clear(DedupeSlot* __restrict__ table, unsigned int size, int* __restrict__ side,
-                               unsigned* __restrict__ fill_a, unsigned long long words_a, unsigned* __restrict__ fill_b,
-                               unsigned long long words_b) {
+// (the body of k_dedupe_clear and of k_dedupe_clear_batch)
+__device__ __forceinline__ void dedupe_clear_body(DedupeSlot* __restrict__ table, unsigned int size, int* __restrict__ side,
+                                                  unsigned* __restrict__ fill_a, unsigned long long words_a,
+                                                  unsigned* __restrict__ fill_b, unsigned long long words_b) {
     const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long w = i; w < words_a; w += stride) fill_a[w] = 0xFFFFFFFFu;
@@ -121,9 +123,15 @@ __global__ void k_dedupe_clear(DedupeSlot* __restrict__ table, unsigned int size
     }
 }
 
+__global__ void k_dedupe_clear(DedupeSlot* __restrict__ table, unsigned int size, int* __restrict__ side,
+                               unsigned* __restrict__ fill_a, unsigned long long words_a, unsigned* __restrict__ fill_b,
+                               unsigned long long words_b) {
+    dedupe_clear_body(table, size, side, fill_a, words_a, fill_b, words_b);
+}
+
 template <typename T>
-__global__ void k_hash_dedupe(const T* __restrict__ xyz, int n, double voxel, DedupeSlot* __restrict__ table,
-                              unsigned int mask, int* __restrict__ side) {
+__device__ __forceinline__ void hash_dedupe_body(const T* __restrict__ xyz, int n, double voxel, DedupeSlot* __restrict__ table,
+                                                 unsigned int mask, int* __restrict__ side) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = i < n;
     unsigned long long h = 0;
@@ -163,15 +171,20 @@ __global__ void k_hash_dedupe(const T* __restrict__ xyz, int n, double voxel, De
     atomicMin(&table[slot].idx, i);
 }
 
+template <typename T>
+__global__ void k_hash_dedupe(const T* __restrict__ xyz, int n, double voxel, DedupeSlot* __restrict__ table,
+                              unsigned int mask, int* __restrict__ side) {
+    hash_dedupe_body<T>(xyz, n, voxel, table, mask, side);
+}
+
 // (a few large workgroups, ONE atomicAdd each: with one per wave — ~3 000 same-address device-scope atomics at 131 072
 // points, ~16 ns apiece — this kernel alone took 52 us)
 static constexpr int COLLECT_THREADS = 1024;
 static constexpr int COLLECT_BLOCKS = 64;
 
-__global__ __launch_bounds__(COLLECT_THREADS) void k_hash_collect(const DedupeSlot* __restrict__ table,
-                                                                  unsigned int size, int* __restrict__ side,
-                                                                  unsigned long long* __restrict__ keys,
-                                                                  int* __restrict__ vals) {
+__device__ __forceinline__ void hash_collect_body(const DedupeSlot* __restrict__ table, unsigned int size,
+                                                  int* __restrict__ side, unsigned long long* __restrict__ keys,
+                                                  int* __restrict__ vals) {
     __shared__ int wave_tot[COLLECT_THREADS / 64];
     __shared__ int base_s;
     // slots [lo, hi) of this workgroup; the side cell (hash == DEDUPE_EMPTY) rides as slot `size`
@@ -211,6 +224,13 @@ __global__ __launch_bounds__(COLLECT_THREADS) void k_hash_collect(const DedupeSl
             ++o;
         }
     }
+}
+
+__global__ __launch_bounds__(COLLECT_THREADS) void k_hash_collect(const DedupeSlot* __restrict__ table,
+                                                                  unsigned int size, int* __restrict__ side,
+                                                                  unsigned long long* __restrict__ keys,
+                                                                  int* __restrict__ vals) {
+    hash_collect_body(table, size, side, keys, vals);
 }
 
 template <typename T>
@@ -469,17 +489,27 @@ static constexpr int BUCKET_BLOCKS = 64;
 static constexpr int BUCKET_THREADS = 512;
 static constexpr int BUCKET_CAP = 4096;
 
+// the workgroup's LDS, declared by the kernel: the batch kernel instantiates the body for two element types on ONE copy
+struct BucketLds {
+    unsigned long long mk[BUCKET_CAP];
+    int mv[BUCKET_CAP];
+    unsigned long long red[2][BUCKET_THREADS / 64];
+    int lower_s[BUCKET_THREADS / 64];
+    int members;
+};
+
+// (the body of k_bucket_sort_emit and of k_bucket_sort_emit_batch; points_f32: a float32 copy of the samples, (float)x)
 template <typename T>
-__global__ __launch_bounds__(BUCKET_THREADS) void k_bucket_sort_emit(const unsigned long long* __restrict__ keys,
-                                                                     const int* __restrict__ vals,
-                                                                     const int* __restrict__ side, const T* __restrict__ xyz,
-                                                                     long long* __restrict__ indices, T* __restrict__ points,
-                                                                     int* __restrict__ count_out) {
-    __shared__ unsigned long long mk[BUCKET_CAP];
-    __shared__ int mv[BUCKET_CAP];
-    __shared__ unsigned long long red[2][BUCKET_THREADS / 64];
-    __shared__ int lower_s[BUCKET_THREADS / 64];
-    __shared__ int members;
+__device__ __forceinline__ void bucket_sort_emit_body(BucketLds& lds, const unsigned long long* __restrict__ keys,
+                                                      const int* __restrict__ vals, const int* __restrict__ side,
+                                                      const T* __restrict__ xyz, long long* __restrict__ indices,
+                                                      T* __restrict__ points, float* __restrict__ points_f32,
+                                                      int* __restrict__ count_out) {
+    unsigned long long* mk = lds.mk;
+    int* mv = lds.mv;
+    auto& red = lds.red;
+    auto& lower_s = lds.lower_s;
+    int& members = lds.members;
     const int V = side[1];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, me = blockIdx.x;
     if (count_out && me == 0 && tid == 0) *count_out = V;
@@ -543,6 +573,11 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_bucket_sort_emit(const unsig
                 points[3 * o + 1] = xyz[3 * src + 1];
                 points[3 * o + 2] = xyz[3 * src + 2];
             }
+            if (points_f32) {
+                points_f32[3 * o] = (float)xyz[3 * src];
+                points_f32[3 * o + 1] = (float)xyz[3 * src + 1];
+                points_f32[3 * o + 2] = (float)xyz[3 * src + 2];
+            }
         }
         return;
     }
@@ -559,7 +594,22 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_bucket_sort_emit(const unsig
             points[3 * rank + 1] = xyz[3 * src + 1];
             points[3 * rank + 2] = xyz[3 * src + 2];
         }
+        if (points_f32) {
+            points_f32[3 * rank] = (float)xyz[3 * src];
+            points_f32[3 * rank + 1] = (float)xyz[3 * src + 1];
+            points_f32[3 * rank + 2] = (float)xyz[3 * src + 2];
+        }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BUCKET_THREADS) void k_bucket_sort_emit(const unsigned long long* __restrict__ keys,
+                                                                     const int* __restrict__ vals,
+                                                                     const int* __restrict__ side, const T* __restrict__ xyz,
+                                                                     long long* __restrict__ indices, T* __restrict__ points,
+                                                                     int* __restrict__ count_out) {
+    __shared__ BucketLds lds;
+    bucket_sort_emit_body<T>(lds, keys, vals, side, xyz, indices, points, (float*)nullptr, count_out);
 }
 
 // padded = true: nothing is read back — the outputs hold n rows, the V samples first, NaN points / index -1 behind them
@@ -738,7 +788,8 @@ int voxel_statistics_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, doubl
 // then per point the Rodrigues rotation by alpha * theta about the axis of the initial motion + alpha * translation,
 // all in float64 like the reference (scipy Slerp + a float64 einsum).
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_minmax_f64(const double* __restrict__ v, int n, double* __restrict__ part) {
+// (the body of k_minmax_f64 and of k_minmax_f64_batch)
+__device__ __forceinline__ void minmax_f64_body(const double* __restrict__ v, int n, double* __restrict__ part) {
     __shared__ double smin[4], smax[4];
     double mn = INFINITY, mx = -INFINITY;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -762,14 +813,20 @@ __global__ __launch_bounds__(256) void k_minmax_f64(const double* __restrict__ v
     }
 }
 
+__global__ __launch_bounds__(256) void k_minmax_f64(const double* __restrict__ v, int n, double* __restrict__ part) {
+    minmax_f64_body(v, n, part);
+}
+
 struct DistortArg {
     double axis[3];
     double theta;
     double t[3];
 };
 
-__global__ void k_distort(const float* __restrict__ xyz, const double* __restrict__ ts, int n,
-                          const double* __restrict__ part, int nparts, DistortArg a, double* __restrict__ out) {
+// (the body of k_distort and of k_distort_batch)
+__device__ __forceinline__ void distort_body(const float* __restrict__ xyz, const double* __restrict__ ts, int n,
+                                             const double* __restrict__ part, int nparts, const DistortArg& a,
+                                             double* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double tmin = INFINITY, tmax = -INFINITY;
@@ -790,14 +847,15 @@ __global__ void k_distort(const float* __restrict__ xyz, const double* __restric
     out[3 * i + 2] = pz * c + cz * s + uz * dot * (1.0 - c) + alpha * a.t[2];
 }
 
-int distort_device(icp_ctx* ctx, const float* xyz_dev, const double* ts_dev, int64_t n, const double* rel_pose16,
-                   double* out_dev) {
-    if (n <= 0) return ICP_OK;
-    const int nparts = 64;
-    ICP_HIP(ctx, ctx->scan_b.reserve((size_t)nparts * 2 * sizeof(double)));
-    double* part = ctx->scan_b.as<double>();
-    hipLaunchKernelGGL(k_minmax_f64, dim3(nparts), dim3(256), 0, ctx->stream, ts_dev, (int)n, part);
-    // log map of the rotation: (R - R^T) / 2 = sin(theta) [axis]x, trace = 1 + 2 cos(theta)
+__global__ void k_distort(const float* __restrict__ xyz, const double* __restrict__ ts, int n,
+                          const double* __restrict__ part, int nparts, DistortArg a, double* __restrict__ out) {
+    distort_body(xyz, ts, n, part, nparts, a, out);
+}
+
+static constexpr int DISTORT_PARTS = 64;  // workgroups of the timestamp min / max
+
+// log map of the rotation: (R - R^T) / 2 = sin(theta) [axis]x, trace = 1 + 2 cos(theta)
+static DistortArg distort_arg(const double* rel_pose16) {
     const double* R = rel_pose16;
     const double vx = 0.5 * (R[9] - R[6]), vy = 0.5 * (R[2] - R[8]), vz = 0.5 * (R[4] - R[1]);
     const double nv = sqrt(vx * vx + vy * vy + vz * vz);
@@ -809,9 +867,268 @@ int distort_device(icp_ctx* ctx, const float* xyz_dev, const double* ts_dev, int
     a.t[0] = R[3];
     a.t[1] = R[7];
     a.t[2] = R[11];
+    return a;
+}
+
+int distort_device(icp_ctx* ctx, const float* xyz_dev, const double* ts_dev, int64_t n, const double* rel_pose16,
+                   double* out_dev) {
+    if (n <= 0) return ICP_OK;
+    const int nparts = DISTORT_PARTS;
+    ICP_HIP(ctx, ctx->scan_b.reserve((size_t)nparts * 2 * sizeof(double)));
+    double* part = ctx->scan_b.as<double>();
+    hipLaunchKernelGGL(k_minmax_f64, dim3(nparts), dim3(256), 0, ctx->stream, ts_dev, (int)n, part);
+    const DistortArg a = distort_arg(rel_pose16);
     hipLaunchKernelGGL(k_distort, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, xyz_dev, ts_dev, (int)n,
                        (const double*)part, nparts, a, out_dev);
     ICP_HIP(ctx, hipGetLastError());
+    return ICP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Distortion -> GridSample(padded) -> ToTensor(float32) for B frames (icp_batch_preprocess, api.hip): ONE launch per kernel
+// kind for the whole batch, blockIdx.y = the member, the per-member arguments by value in the kernel-argument segment (one
+// small struct per kernel: the pointers reach the kernels as global pointers, no flat memory instructions).  The bodies are
+// those of the single kernels above.  A de-skewed member is sampled from its float64 rows (GridSample on Distortion's
+// output), any other member from its float32 rows: the element type is a per-member flag, uniform in the workgroup.  A member
+// above the bucket sort's bound takes the single path (grid_sample_impl) on its own context, in the same call.
+// ---------------------------------------------------------------------------------------------------------------------
+struct MinmaxBatchEntry {
+    const double* ts;
+    double* part;
+    int n;
+};
+struct MinmaxBatchArgs {
+    MinmaxBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
+};
+struct DistortBatchEntry {
+    const float* xyz;
+    const double* ts;
+    const double* part;
+    double* out;
+    DistortArg a;
+    int n;
+};
+struct DistortBatchArgs {
+    DistortBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
+};
+struct ClearBatchEntry {
+    DedupeSlot* table;
+    int* side;
+    unsigned* fill_a;  // the samples (member's element type)
+    unsigned* fill_b;  // the indices
+    unsigned* fill_c;  // the float32 copy of the samples
+    unsigned long long words_a, words_b, words_c;
+    unsigned size;
+};
+struct ClearBatchArgs {
+    ClearBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
+};
+struct DedupeBatchEntry {
+    const void* xyz;
+    DedupeSlot* table;
+    int* side;
+    int n;
+    unsigned mask;
+    int f64;
+};
+struct DedupeBatchArgs {
+    DedupeBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
+};
+struct CollectBatchEntry {
+    const DedupeSlot* table;
+    int* side;
+    unsigned long long* keys;
+    int* vals;
+    unsigned size;
+};
+struct CollectBatchArgs {
+    CollectBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
+};
+struct EmitBatchEntry {
+    const unsigned long long* keys;
+    const int* vals;
+    const int* side;
+    const void* xyz;
+    long long* indices;
+    void* points;
+    float* points_f32;
+    int* count;
+    int f64;
+};
+struct EmitBatchArgs {
+    EmitBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
+};
+static_assert(sizeof(MinmaxBatchArgs) <= 4096 && sizeof(DistortBatchArgs) <= 4096 && sizeof(ClearBatchArgs) <= 4096 &&
+                  sizeof(DedupeBatchArgs) <= 4096 && sizeof(CollectBatchArgs) <= 4096 && sizeof(EmitBatchArgs) <= 4096,
+              "the per-member arguments of a batch kernel must fit the 4 KB kernel-argument segment");
+
+__global__ __launch_bounds__(256) void k_minmax_f64_batch(MinmaxBatchArgs a) {
+    const MinmaxBatchEntry& e = a.e[blockIdx.y];
+    minmax_f64_body(e.ts, e.n, e.part);
+}
+
+__global__ void k_distort_batch(DistortBatchArgs a) {
+    const DistortBatchEntry& e = a.e[blockIdx.y];
+    distort_body(e.xyz, e.ts, e.n, e.part, DISTORT_PARTS, e.a, e.out);
+}
+
+__global__ void k_dedupe_clear_batch(ClearBatchArgs a) {
+    const ClearBatchEntry& e = a.e[blockIdx.y];
+    dedupe_clear_body(e.table, e.size, e.side, e.fill_a, e.words_a, e.fill_b, e.words_b);
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long w = blockIdx.x * blockDim.x + threadIdx.x; w < e.words_c; w += stride) e.fill_c[w] = 0xFFFFFFFFu;
+}
+
+__global__ void k_hash_dedupe_batch(DedupeBatchArgs a, double voxel) {
+    const DedupeBatchEntry& e = a.e[blockIdx.y];
+    if ((long long)blockIdx.x * blockDim.x >= (long long)e.n) return;  // (workgroup-uniform)
+    if (e.f64)
+        hash_dedupe_body<double>(static_cast<const double*>(e.xyz), e.n, voxel, e.table, e.mask, e.side);
+    else
+        hash_dedupe_body<float>(static_cast<const float*>(e.xyz), e.n, voxel, e.table, e.mask, e.side);
+}
+
+__global__ __launch_bounds__(COLLECT_THREADS) void k_hash_collect_batch(CollectBatchArgs a) {
+    const CollectBatchEntry& e = a.e[blockIdx.y];
+    hash_collect_body(e.table, e.size, e.side, e.keys, e.vals);
+}
+
+__global__ __launch_bounds__(BUCKET_THREADS) void k_bucket_sort_emit_batch(EmitBatchArgs a) {
+    __shared__ BucketLds lds;
+    const EmitBatchEntry& e = a.e[blockIdx.y];
+    if (e.f64)
+        bucket_sort_emit_body<double>(lds, e.keys, e.vals, e.side, static_cast<const double*>(e.xyz), e.indices,
+                                      static_cast<double*>(e.points), e.points_f32, e.count);
+    else
+        bucket_sort_emit_body<float>(lds, e.keys, e.vals, e.side, static_cast<const float*>(e.xyz), e.indices,
+                                     static_cast<float*>(e.points), e.points_f32, e.count);
+}
+
+// the float32 copy of a member that took the single path: (float)x, padding included (NaN stays NaN)
+__global__ void k_rows_to_f32(const double* __restrict__ in, long long count, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = (float)in[i];
+}
+
+static constexpr int64_t BUCKET_MAX_ROWS = 262144;  // (grid_sample_impl's bound of the bucket sort in the padded path)
+
+int preprocess_batch_device(icp_ctx* const* ctxs, int count, const icp_preprocess_frame* frames, double voxel) {
+    icp_ctx* first = ctxs[0];
+    MinmaxBatchArgs mm;
+    DistortBatchArgs ds;
+    ClearBatchArgs cl;
+    DedupeBatchArgs dd;
+    CollectBatchArgs co;
+    EmitBatchArgs em;
+    memset(&mm, 0, sizeof(mm));
+    memset(&ds, 0, sizeof(ds));
+    memset(&cl, 0, sizeof(cl));
+    memset(&dd, 0, sizeof(dd));
+    memset(&co, 0, sizeof(co));
+    memset(&em, 0, sizeof(em));
+    int n_skew = 0, n_grid = 0, fallback[ICP_BATCH_MAX_SEQUENCES], n_fallback = 0;
+    unsigned skew_blocks = 1, clear_blocks = 1, dedupe_blocks = 1;
+    for (int b = 0; b < count; ++b) {
+        icp_ctx* ctx = ctxs[b];
+        const icp_preprocess_frame& f = frames[b];
+        const int64_t n = f.n;
+        const bool f64 = f.timestamps != nullptr;
+        if (f64 && n > 0) {  // the de-skew (Distortion.filter, slam/preprocessing.py:144-191)
+            ICP_HIP(ctx, ctx->scan_b.reserve((size_t)DISTORT_PARTS * 2 * sizeof(double)));
+            double* part = ctx->scan_b.as<double>();
+            mm.e[n_skew] = MinmaxBatchEntry{f.timestamps, part, (int)n};
+            DistortBatchEntry& d = ds.e[n_skew];
+            d.xyz = f.xyz;
+            d.ts = f.timestamps;
+            d.part = part;
+            d.out = f.distorted_out;
+            d.a = distort_arg(f.rel_pose);
+            d.n = (int)n;
+            skew_blocks = std::max(skew_blocks, (unsigned)((n + 255) / 256));
+            ++n_skew;
+        }
+        if (n > BUCKET_MAX_ROWS) {
+            fallback[n_fallback++] = b;
+            continue;
+        }
+        // the grid sample (GridSample.filter, slam/preprocessing.py:207-226), padded; an empty member rides along (its count: 0)
+        unsigned int tsize = 0;
+        if (n > 0) {
+            tsize = 1024;
+            while ((int64_t)tsize < 2 * n) tsize <<= 1;
+            ICP_HIP(ctx, ctx->keys_a.reserve((size_t)tsize * sizeof(DedupeSlot)));
+            ICP_HIP(ctx, ctx->keys_b.reserve((size_t)n * 8));
+            ICP_HIP(ctx, ctx->vals_a.reserve((size_t)n * 4));
+        }
+        ICP_HIP(ctx, ctx->flags.reserve(64));
+        DedupeSlot* table = ctx->keys_a.as<DedupeSlot>();
+        int* side = ctx->flags.as<int>();
+        const size_t elem_words = f64 ? 2 : 1;
+        const void* src = f64 ? (const void*)f.distorted_out : (const void*)f.xyz;
+        ClearBatchEntry& c = cl.e[n_grid];
+        c.table = table;
+        c.side = side;
+        c.fill_a = reinterpret_cast<unsigned*>(f.samples_out);
+        c.words_a = f.samples_out ? (unsigned long long)n * 3 * elem_words : 0ull;
+        c.fill_b = reinterpret_cast<unsigned*>(f.indices_out);
+        c.words_b = f.indices_out ? (unsigned long long)n * 2 : 0ull;
+        c.fill_c = reinterpret_cast<unsigned*>(f.samples_f32_out);
+        c.words_c = f.samples_f32_out ? (unsigned long long)n * 3 : 0ull;
+        c.size = tsize;
+        dd.e[n_grid] = DedupeBatchEntry{src, table, side, (int)n, tsize ? tsize - 1 : 0u, f64 ? 1 : 0};
+        co.e[n_grid] = CollectBatchEntry{table, side, ctx->keys_b.as<unsigned long long>(), ctx->vals_a.as<int>(), tsize};
+        EmitBatchEntry& m = em.e[n_grid];
+        m.keys = ctx->keys_b.as<unsigned long long>();
+        m.vals = ctx->vals_a.as<int>();
+        m.side = side;
+        m.xyz = src;
+        m.indices = (long long*)f.indices_out;
+        m.points = f.samples_out;
+        m.points_f32 = f.samples_f32_out;
+        m.count = f.count_out;
+        m.f64 = f64 ? 1 : 0;
+        clear_blocks = std::max(clear_blocks, (tsize + 255) / 256);
+        dedupe_blocks = std::max(dedupe_blocks, (unsigned)((n + 255) / 256));
+        ++n_grid;
+    }
+    hipStream_t st = first->stream;
+    if (n_skew) {
+        hipLaunchKernelGGL(k_minmax_f64_batch, dim3(DISTORT_PARTS, n_skew), dim3(256), 0, st, mm);
+        hipLaunchKernelGGL(k_distort_batch, dim3(skew_blocks, n_skew), dim3(256), 0, st, ds);
+    }
+    if (n_grid) {
+        hipLaunchKernelGGL(k_dedupe_clear_batch, dim3(clear_blocks, n_grid), dim3(256), 0, st, cl);
+        hipLaunchKernelGGL(k_hash_dedupe_batch, dim3(dedupe_blocks, n_grid), dim3(256), 0, st, dd, voxel);
+        hipLaunchKernelGGL(k_hash_collect_batch, dim3(COLLECT_BLOCKS, n_grid), dim3(COLLECT_THREADS), 0, st, co);
+        hipLaunchKernelGGL(k_bucket_sort_emit_batch, dim3(BUCKET_BLOCKS, n_grid), dim3(BUCKET_THREADS), 0, st, em);
+    }
+    ICP_HIP(first, hipGetLastError());
+    // members above the bucket sort's bound: the single path, then their float32 copy
+    for (int k = 0; k < n_fallback; ++k) {
+        icp_ctx* ctx = ctxs[fallback[k]];
+        const icp_preprocess_frame& f = frames[fallback[k]];
+        const int64_t n = f.n;
+        int unused = 0;
+        if (f.timestamps) {
+            double* pts = static_cast<double*>(f.samples_out);
+            if (!pts) {
+                ICP_HIP(ctx, ctx->vox_out.reserve((size_t)n * 24));
+                pts = ctx->vox_out.as<double>();
+            }
+            int rc = grid_sample_impl<double>(ctx, f.distorted_out, n, voxel, (long long*)f.indices_out, pts, f.count_out,
+                                              &unused, true);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_rows_to_f32, dim3((unsigned)((3 * n + 255) / 256)), dim3(256), 0, ctx->stream,
+                               (const double*)pts, (long long)(3 * n), f.samples_f32_out);
+        } else {
+            float* pts = f.samples_out ? static_cast<float*>(f.samples_out) : f.samples_f32_out;
+            int rc = grid_sample_impl<float>(ctx, f.xyz, n, voxel, (long long*)f.indices_out, pts, f.count_out, &unused, true);
+            if (rc) return rc;
+            if (pts != f.samples_f32_out)
+                ICP_HIP(ctx, hipMemcpyAsync(f.samples_f32_out, pts, (size_t)n * 12, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        ICP_HIP(ctx, hipGetLastError());
+    }
     return ICP_OK;
 }
 

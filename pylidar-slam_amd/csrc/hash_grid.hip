@@ -8,6 +8,7 @@
 // The rank order inside a cell is not deterministic, but every consumer breaks distance ties on the ORIGINAL index,
 // so search results are.
 #include <math.h>
+#include <string.h>
 
 #include "icp_internal.h"
 #include "map_move_device.h"
@@ -173,28 +174,34 @@ __device__ inline int row_is_valid(const float* __restrict__ xyz, long long i, l
     return (skip_null && x == 0.f && y == 0.f && z == 0.f) ? 0 : 1;
 }
 
-__global__ __launch_bounds__(CV_THREADS) void k_valid_tile_counts(const float* __restrict__ xyz, long long n,
-                                                                  int skip_null, int* __restrict__ counts) {
+// (the bodies of k_valid_tile_counts / k_valid_compact and of their batch forms: `tile` = the workgroup's tile of its cloud)
+__device__ __forceinline__ void valid_tile_counts_body(const float* __restrict__ xyz, long long n, int skip_null,
+                                                       int* __restrict__ counts, int tile) {
     __shared__ int lds[8];
-    const long long base = (long long)blockIdx.x * CV_TILE + threadIdx.x;
+    const long long base = (long long)tile * CV_TILE + threadIdx.x;
     int s = 0;
 #pragma unroll
     for (int k = 0; k < CV_ROUNDS; ++k) s += row_is_valid(xyz, base + (long long)k * CV_THREADS, n, skip_null);
     int tot;
     block_exclusive_scan(s, &tot, lds);
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+    if (threadIdx.x == 0) counts[tile] = tot;
 }
 
-__global__ __launch_bounds__(CV_THREADS) void k_valid_compact(const float* __restrict__ xyz, long long n, int skip_null,
-                                                              const int* __restrict__ counts, float* __restrict__ out,
-                                                              long long cap, int* __restrict__ count_dev,
-                                                              int* __restrict__ count_host) {
+__global__ __launch_bounds__(CV_THREADS) void k_valid_tile_counts(const float* __restrict__ xyz, long long n,
+                                                                  int skip_null, int* __restrict__ counts) {
+    valid_tile_counts_body(xyz, n, skip_null, counts, (int)blockIdx.x);
+}
+
+__device__ __forceinline__ void valid_compact_body(const float* __restrict__ xyz, long long n, int skip_null,
+                                                   const int* __restrict__ counts, float* __restrict__ out, long long cap,
+                                                   int* __restrict__ count_dev, int* __restrict__ count_host, int tile,
+                                                   bool last_tile) {
     __shared__ int lds[8];
     int before = 0;
-    for (int t = threadIdx.x; t < (int)blockIdx.x; t += CV_THREADS) before += counts[t];
+    for (int t = threadIdx.x; t < tile; t += CV_THREADS) before += counts[t];
     int running;
     block_exclusive_scan(before, &running, lds);  // (total of the tiles in front)
-    const long long base = (long long)blockIdx.x * CV_TILE + threadIdx.x;
+    const long long base = (long long)tile * CV_TILE + threadIdx.x;
 #pragma unroll
     for (int k = 0; k < CV_ROUNDS; ++k) {  // rows base + k * 256 + thread: round by round in row order
         const long long i = base + (long long)k * CV_THREADS;
@@ -208,10 +215,46 @@ __global__ __launch_bounds__(CV_THREADS) void k_valid_compact(const float* __res
         }
         running += tot;
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    if (last_tile && threadIdx.x == 0) {
         if (count_dev) *count_dev = running;
         if (count_host) __hip_atomic_store(count_host, running, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+__global__ __launch_bounds__(CV_THREADS) void k_valid_compact(const float* __restrict__ xyz, long long n, int skip_null,
+                                                              const int* __restrict__ counts, float* __restrict__ out,
+                                                              long long cap, int* __restrict__ count_dev,
+                                                              int* __restrict__ count_host) {
+    valid_compact_body(xyz, n, skip_null, counts, out, cap, count_dev, count_host, (int)blockIdx.x,
+                       blockIdx.x == gridDim.x - 1);
+}
+
+// ... for B clouds in two launches (icp_batch_stage): blockIdx.y = the member, its arguments by value in the kernel-argument
+// segment; the workgroups beyond a member's own tiles return at once, the member's last tile stores its count
+struct CompactBatchEntry {
+    const float* xyz;
+    int* counts;
+    float* out;
+    int* count_host;
+    long long n;
+    int tiles;
+};
+struct CompactBatchArgs {
+    CompactBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
+};
+static_assert(sizeof(CompactBatchArgs) <= 4096, "the per-member arguments must fit the 4 KB kernel-argument segment");
+
+__global__ __launch_bounds__(CV_THREADS) void k_valid_tile_counts_batch(CompactBatchArgs a, int skip_null) {
+    const CompactBatchEntry& e = a.e[blockIdx.y];
+    if ((int)blockIdx.x >= e.tiles) return;
+    valid_tile_counts_body(e.xyz, e.n, skip_null, e.counts, (int)blockIdx.x);
+}
+
+__global__ __launch_bounds__(CV_THREADS) void k_valid_compact_batch(CompactBatchArgs a, int skip_null) {
+    const CompactBatchEntry& e = a.e[blockIdx.y];
+    if ((int)blockIdx.x >= e.tiles) return;
+    valid_compact_body(e.xyz, e.n, skip_null, e.counts, e.out, e.n, nullptr, e.count_host, (int)blockIdx.x,
+                       (int)blockIdx.x == e.tiles - 1);
 }
 
 int compact_valid_rows(icp_ctx* ctx, const float* xyz, int64_t n, bool skip_null, float* out, int* count_dev,
@@ -228,6 +271,28 @@ int compact_valid_rows(icp_ctx* ctx, const float* xyz, int64_t n, bool skip_null
     hipLaunchKernelGGL(k_valid_compact, dim3(nb), dim3(CV_THREADS), 0, ctx->stream, xyz, (long long)n, skip_null ? 1 : 0,
                        counts, out, (long long)(cap >= 0 ? cap : n), count_dev, count_host_mapped);
     ICP_HIP(ctx, hipGetLastError());
+    return ICP_OK;
+}
+
+int compact_valid_rows_batch(icp_ctx* const* ctxs, int count, const float* const* xyz, const int64_t* n, bool skip_null,
+                             float* const* out, int* const* count_host_mapped) {
+    CompactBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    int max_tiles = 0;
+    for (int b = 0; b < count; ++b) {
+        icp_ctx* ctx = ctxs[b];
+        const int nb = n[b] > 0 ? (int)((n[b] + CV_TILE - 1) / CV_TILE) : 0;
+        if (nb) {
+            ICP_HIP(ctx, ctx->scan_tmp.reserve((size_t)nb * sizeof(int)));
+        }
+        a.e[b] = CompactBatchEntry{xyz[b], ctx->scan_tmp.as<int>(), out[b], count_host_mapped[b], (long long)n[b], nb};
+        max_tiles = nb > max_tiles ? nb : max_tiles;
+    }
+    if (max_tiles == 0) return ICP_OK;
+    hipStream_t st = ctxs[0]->stream;
+    hipLaunchKernelGGL(k_valid_tile_counts_batch, dim3(max_tiles, count), dim3(CV_THREADS), 0, st, a, skip_null ? 1 : 0);
+    hipLaunchKernelGGL(k_valid_compact_batch, dim3(max_tiles, count), dim3(CV_THREADS), 0, st, a, skip_null ? 1 : 0);
+    ICP_HIP(ctxs[0], hipGetLastError());
     return ICP_OK;
 }
 

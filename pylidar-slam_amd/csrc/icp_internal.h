@@ -711,7 +711,14 @@ int launch_procrustes_pass(icp_ctx* ctx, const float* tgt, const float* ref, con
 int project_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* vmap_dev, int32_t* index_dev, bool keep_keys = false,
                    float* rows_dev = nullptr);
 int project_pixels_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* rows_dev, float* cols_dev);
-int project_batch_device(icp_ctx* const* ctxs, int count, const float* const* xyz_dev, const int64_t* n, float* const* vmap_dev);
+// rows_dev (optional; entries may be NULL): the same pixels as [H*W, 3] rows, as project_device's rows_dev
+int project_batch_device(icp_ctx* const* ctxs, int count, const float* const* xyz_dev, const int64_t* n, float* const* vmap_dev,
+                         float* const* rows_dev = nullptr);
+// Distortion -> GridSample(padded) -> ToTensor(float32) for `count` frames (icp_batch_preprocess), on ctxs[0]'s stream
+int preprocess_batch_device(icp_ctx* const* ctxs, int count, const icp_preprocess_frame* frames, double voxel);
+// icp_map_stage_cloud's compaction for `count` clouds in two launches (skipped members: n[b] == 0)
+int compact_valid_rows_batch(icp_ctx* const* ctxs, int count, const float* const* xyz, const int64_t* n, bool skip_null,
+                             float* const* out, int* const* count_host_mapped);
 int kitti_correct_device(icp_ctx* ctx, const float* scan_dev, int64_t n, int stride, double* out_dev);
 
 // ---- projective.hip

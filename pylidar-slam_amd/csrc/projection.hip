@@ -85,17 +85,20 @@ __global__ void k_project_resolve(const float* __restrict__ xyz, unsigned long l
 }
 
 // B projections per launch (icp_batch_project): blockIdx.y = the member; its arguments ride in the kernel-argument segment
-// (48 bytes per member).  Same arithmetic per point and per pixel as k_project / k_project_resolve.
+// (56 bytes per member).  Same arithmetic per point and per pixel as k_project / k_project_resolve; `rows` (may be NULL): the
+// same pixels as [H*W, 3] rows, as k_project_resolve writes them (icp_batch_project_rows).
 struct ProjBatchEntry {
     const float* xyz;
     unsigned long long* zbuf;
     float* vmap;
+    float* rows;
     int n, npix;
     ProjParams pp;
 };
 struct ProjBatchArgs {
     ProjBatchEntry e[ICP_BATCH_MAX_SEQUENCES];
 };
+static_assert(sizeof(ProjBatchArgs) <= 4096, "the per-member arguments must fit the 4 KB kernel-argument segment");
 
 __global__ void k_project_batch(ProjBatchArgs a) {
     const ProjBatchEntry& e = a.e[blockIdx.y];
@@ -128,6 +131,11 @@ __global__ void k_project_resolve_batch(ProjBatchArgs a) {
     e.vmap[p] = x;
     e.vmap[e.npix + p] = y;
     e.vmap[2 * e.npix + p] = z;
+    if (e.rows) {
+        e.rows[3 * p] = x;
+        e.rows[3 * p + 1] = y;
+        e.rows[3 * p + 2] = z;
+    }
 }
 
 __global__ void k_project_pixels(const float* __restrict__ xyz, int n, ProjParams pp, float* __restrict__ rows,
@@ -206,7 +214,8 @@ int project_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* vmap_de
 }
 
 // vertex maps of `count` scans (device pointers) in two launches; every member keeps its own z-buffer
-int project_batch_device(icp_ctx* const* ctxs, int count, const float* const* xyz_dev, const int64_t* n, float* const* vmap_dev) {
+int project_batch_device(icp_ctx* const* ctxs, int count, const float* const* xyz_dev, const int64_t* n, float* const* vmap_dev,
+                         float* const* rows_dev) {
     ProjBatchArgs a;
     memset(&a, 0, sizeof(a));
     int max_n = 0, max_pix = 0;
@@ -224,6 +233,7 @@ int project_batch_device(icp_ctx* const* ctxs, int count, const float* const* xy
         a.e[b].xyz = xyz_dev[b];
         a.e[b].zbuf = zb;
         a.e[b].vmap = vmap_dev[b];
+        a.e[b].rows = rows_dev ? rows_dev[b] : nullptr;
         a.e[b].n = (int)n[b];
         a.e[b].npix = npix;
         a.e[b].pp = proj_params(ctx);

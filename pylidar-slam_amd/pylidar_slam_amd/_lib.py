@@ -9,8 +9,8 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "load_library", "library_path", "EXPORTED_SYMBOLS",
-           "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
+__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "load_library", "library_path",
+           "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
 
 MEM_HOST, MEM_DEVICE = 0, 1
 TARGETS_ALL, TARGETS_SKIP_NULL = 0, 1
@@ -49,6 +49,13 @@ class IcpConfig(C.Structure):
                 ("max_num_alignments", C.c_int32), ("threshold_delta_pose", C.c_float), ("scheme", C.c_int32),
                 ("sigma", C.c_float), ("local_map_size", C.c_int32), ("num_neighbors_normals", C.c_int32),
                 ("cell_size", C.c_float), ("max_rings", C.c_int32), ("device", C.c_int32), ("poll_every", C.c_int32)]
+
+
+class IcpPreprocessFrame(C.Structure):
+    """icp_preprocess_frame: one member's frame of icp_batch_preprocess (device pointers)."""
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_int64), ("timestamps", C.c_void_p), ("rel_pose", C.c_double * 16),
+                ("distorted_out", C.c_void_p), ("samples_out", C.c_void_p), ("samples_f32_out", C.c_void_p),
+                ("indices_out", C.c_void_p), ("count_out", C.c_void_p)]
 
 
 class IcpRegisterResult(C.Structure):
@@ -131,6 +138,9 @@ EXPORTED_SYMBOLS = {
     "icp_batch_pmap_register_launch": (_INT, [_P, _P, _P, _INT, _INT, _P, _INT]),
     "icp_batch_pmap_update": (_INT, [_P, _P, _P, _INT, _INT]),
     "icp_batch_register_end": (_INT, [_P, _P, _P, _P]),
+    "icp_batch_preprocess": (_INT, [_P, C.POINTER(IcpPreprocessFrame), C.c_double]),
+    "icp_batch_project_rows": (_INT, [_P, _P, _P, _P, _P]),
+    "icp_batch_stage": (_INT, [_P, _P, _P, _INT]),
     "icp_normal_equations_ptr": (_P, [_P]),
     "icp_set_normal_equations_buffer": (_INT, [_P, _P]),
     "icp_profile_enable": (_INT, [_P, _INT]),

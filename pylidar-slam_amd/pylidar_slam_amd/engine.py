@@ -12,8 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (COSTS, IcpConfig, IcpLibraryError, IcpRegisterResult, MEM_DEVICE, MEM_HOST, SCHEMES,
-                   STATUS_MESSAGES, TARGETS_ALL, TARGETS_SKIP_NULL)
+from ._lib import (COSTS, IcpConfig, IcpLibraryError, IcpPreprocessFrame, IcpRegisterResult, MEM_DEVICE, MEM_HOST,
+                   SCHEMES, STATUS_MESSAGES, TARGETS_ALL, TARGETS_SKIP_NULL)
 
 Array = Union[np.ndarray, torch.Tensor]
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> raw hipStream_t of torch's current stream
@@ -858,12 +858,134 @@ class IcpBatch:
         self._check(self._lib.icp_batch_map_update(self._h))
 
     def stage(self, clouds, skip_null: bool = False):
-        """`IcpContext.map_stage_cloud(clouds[b])` on every member (one staging call each): the clouds a later
-        `map_update_staged` inserts."""
-        if len(clouds) != len(self.contexts):
-            raise AssertionError(f"expected {len(self.contexts)} clouds, got {len(clouds)}")
-        for c, pts in zip(self.contexts, clouds):
-            c.map_stage_cloud(pts, skip_null=skip_null)
+        """`IcpContext.map_stage_cloud(clouds[b])` on every member in ONE call, two launches (icp_batch_stage): the clouds
+        ([n_b, 3] float32 cuda tensors) a later `map_update_staged` inserts."""
+        b = len(self.contexts)
+        if len(clouds) != b:
+            raise AssertionError(f"expected {b} clouds, got {len(clouds)}")
+        keep = [self._device_rows(pts, "batched staging") for pts in clouds]
+        self.use_torch_stream()
+        xyz = (C.c_void_p * b)(*[k.data_ptr() if k.shape[0] else None for k in keep])
+        n = (C.c_int64 * b)(*[int(k.shape[0]) for k in keep])
+        self._keep_staged = keep  # (read by the enqueued launches)
+        self._check(self._lib.icp_batch_stage(self._h, xyz, n, TARGETS_SKIP_NULL if skip_null else TARGETS_ALL))
+
+    @staticmethod
+    def _device_rows(a, what: str) -> torch.Tensor:
+        """[n, 3] float32 contiguous cuda rows (a float32 view of a cuda tensor of another dtype / layout is made here)."""
+        if not (isinstance(a, torch.Tensor) and a.is_cuda):
+            raise AssertionError(f"{what} takes cuda tensors (device pointers), got {type(a).__name__}"
+                                 f"{'' if not isinstance(a, torch.Tensor) else ' on ' + str(a.device)}")
+        t = a if (a.dtype == torch.float32 and a.is_contiguous()) else a.to(torch.float32).contiguous()
+        if t.ndim != 2 or t.shape[1] != 3:
+            raise AssertionError(f"{what}: expected [n, 3] rows, got {tuple(t.shape)}")
+        return t
+
+    def project_rows(self, scans, rows=True):
+        """`IcpContext.project_rows(scans[b])` for every member in two launches (icp_batch_project_rows): a list of
+        (vertex map [3, H, W], rows [H * W, 3]) per member.  `rows`: False, or a list of flags — the members without rows
+        get their vertex map only (None in place of the rows; the same launches as `project`)."""
+        b = len(self.contexts)
+        if len(scans) != b:
+            raise AssertionError(f"expected {b} scans, got {len(scans)}")
+        flags = [bool(rows)] * b if isinstance(rows, bool) else [bool(r) for r in rows]
+        if len(flags) != b:
+            raise AssertionError(f"expected {b} row flags, got {len(flags)}")
+        keep = [self._device_rows(a, "batched projection") for a in scans]
+        self.use_torch_stream()
+        out = []
+        for c, k, r in zip(self.contexts, keep, flags):
+            h, w = c.config.height, c.config.width
+            out.append((torch.empty((3, h, w), dtype=torch.float32, device=k.device),
+                        torch.empty((h * w, 3), dtype=torch.float32, device=k.device) if r else None))
+        xyz = (C.c_void_p * b)(*[k.data_ptr() if k.shape[0] else None for k in keep])
+        n = (C.c_int64 * b)(*[int(k.shape[0]) for k in keep])
+        vm = (C.c_void_p * b)(*[v.data_ptr() for v, _ in out])
+        rw = (C.c_void_p * b)(*[r.data_ptr() if r is not None else None for _, r in out])
+        self._keep_projected = keep
+        self._check(self._lib.icp_batch_project_rows(self._h, xyz, n, vm, rw))
+        return out
+
+    def preprocess(self, points, timestamps, rel_poses, voxel_size: float, out=None):
+        """`Distortion` -> `GridSample(padded)` -> `ToTensor(float32)` (slam/preprocessing.py:144-191, :207-226, :101-126)
+        for every member in one call (icp_batch_preprocess): two launches de-skew, four sample, nothing is read back.
+
+        points[b]: [n_b, 3] float32 cuda tensor; timestamps[b]: [n_b] float64 cuda tensor — the frame is de-skewed by
+        rel_poses[b] (4x4) and sampled from its float64 rows — or None (Distortion's pass-through: sampled from its float32
+        rows).  Returns `out` (allocated when None): one dict per member with `distorted` ([n, 3] float64, None without
+        timestamps), `samples` ([n, 3] in the member's dtype), `samples_f32` ([n, 3] float32; for a float32 member the very
+        same tensor as `samples`), `indices` ([n] int64) and `count` (0-dim int32 cuda tensor, V): the V samples by ascending
+        voxel hash first, NaN rows / index -1 behind them — per member the bits of `IcpContext.distort` +
+        `grid_sample_padded` + a float32 cast.  Entries of a given `out` may be None (`distorted` of a de-skewed member:
+        the call is refused)."""
+        b = len(self.contexts)
+        if len(points) != b or len(timestamps) != b or len(rel_poses) != b:
+            raise AssertionError(f"expected {b} frames, timestamps and relative poses, got "
+                                 f"{len(points)} / {len(timestamps)} / {len(rel_poses)}")
+        pts = []
+        for k, a in enumerate(points):
+            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32):
+                raise AssertionError(f"batched preprocessing, member {k}: the points must be a float32 cuda tensor")
+            pts.append(self._device_rows(a, f"batched preprocessing, member {k}"))
+        ts = []
+        for k, (t, p) in enumerate(zip(timestamps, pts)):
+            if t is None:
+                ts.append(None)
+                continue
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+                raise AssertionError(f"batched preprocessing, member {k}: the timestamps must be a float64 cuda tensor")
+            t = t.reshape(-1).contiguous()
+            if t.shape[0] != p.shape[0]:
+                raise AssertionError(f"batched preprocessing, member {k}: {t.shape[0]} timestamps for {p.shape[0]} points")
+            ts.append(t)
+        if out is None:
+            out = []
+            for p, t in zip(pts, ts):
+                n, dev = int(p.shape[0]), p.device
+                f32 = torch.empty((n, 3), dtype=torch.float32, device=dev)
+                out.append({"distorted": torch.empty((n, 3), dtype=torch.float64, device=dev) if t is not None else None,
+                            "samples": torch.empty((n, 3), dtype=torch.float64, device=dev) if t is not None else f32,
+                            "samples_f32": f32, "indices": torch.empty(n, dtype=torch.int64, device=dev),
+                            "count": torch.empty((), dtype=torch.int32, device=dev)})
+        if len(out) != b:
+            raise AssertionError(f"expected {b} output sets, got {len(out)}")
+        for k, o in enumerate(out):
+            for key in ("distorted", "samples", "samples_f32", "indices", "count"):
+                v = o.get(key)
+                if v is not None and not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
+                    raise AssertionError(f"batched preprocessing, member {k}: `{key}` must be a contiguous cuda tensor")
+        frames = (IcpPreprocessFrame * b)()
+        rel_off = IcpPreprocessFrame.rel_pose.offset
+        poses = []
+        for k, (p, t, o) in enumerate(zip(pts, ts, out)):
+            f = frames[k]
+            n = int(p.shape[0])
+            f.xyz = p.data_ptr() if n else None
+            f.n = n
+            if t is not None:
+                f.timestamps = t.data_ptr() if n else None
+                pose = np.ascontiguousarray(np.asarray(rel_poses[k], dtype=np.float64).reshape(16))
+                poses.append(pose)
+                C.memmove(C.addressof(f) + rel_off, pose.ctypes.data, 128)
+
+            def ptr(key, dtype=None):
+                v = o.get(key)
+                if v is None or n == 0 and key != "count":
+                    return None
+                if dtype is not None and v.dtype != dtype:
+                    raise AssertionError(f"batched preprocessing, member {k}: `{key}` must be {dtype}")
+                return v.data_ptr()
+            f.distorted_out = ptr("distorted", torch.float64)
+            smp = o.get("samples")
+            f.samples_out = None if (smp is None or smp is o.get("samples_f32")) else \
+                ptr("samples", torch.float64 if t is not None else torch.float32)
+            f.samples_f32_out = ptr("samples_f32", torch.float32)
+            f.indices_out = ptr("indices", torch.int64)
+            f.count_out = ptr("count", torch.int32)
+        self.use_torch_stream()
+        self._keep_preprocessed = (pts, ts)  # (read by the enqueued launches)
+        self._check(self._lib.icp_batch_preprocess(self._h, frames, float(voxel_size)))
+        return out
 
     def map_update_staged(self, insert, rel_poses=None):
         """`ICPFrameToModel.__update_map` for every member (icp_batch_map_update_staged): member b inserts the cloud it

@@ -33,7 +33,7 @@ __all__ = ["OdometryAlgorithm", "MI355XICPConfig", "MI355XICPFrameToModel", "Has
            "PointToPlaneAlignmentConfig", "PointToPointAlignment", "PointToPointAlignmentConfig", "SphericalProjector",
            "GridSample", "GridSampleConfig", "grid_sample", "Distortion", "DistortionConfig", "Voxelization",
            "VoxelizationConfig", "ToDevice", "ToDeviceConfig", "ConstantVelocityInitialization", "NeighborhoodResult",
-           "MI355XICPFrameToModelBatch",
+           "MI355XICPFrameToModelBatch", "MI355XPreprocessingBatch",
            "build_pose_matrix", "from_pose_matrix"]
 
 
@@ -387,6 +387,203 @@ class Distortion:
         if _is_device_tensor(pc):
             ctx.use_torch_stream()
         data_dict[c.output_key] = ctx.distort(pc, timestamps, rpose)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+class _PackedUpload:
+    """`ToDevice._upload` for the B arrays of one key: one host copy each into ONE persistent pinned buffer, ONE DMA on an
+    upload stream of its own into one of two alternating device slots, the caller's stream made to wait for it.  The
+    tensors a call returns are views of that slot: overwritten TWO calls later (ToDevice's rule)."""
+
+    def __init__(self, device):
+        self.device = device
+        self.pin = None
+        self.free = None
+        self.dev = [None, None]
+        self.used = [None, None]
+        self.which = 0
+        self.stream = None
+
+    def __call__(self, arrays):
+        sizes = [int(a.size) for a in arrays]
+        total = sum(sizes)
+        if total == 0:
+            return [torch.from_numpy(a).to(self.device) for a in arrays]
+        tdtype = torch.from_numpy(arrays[0][:0]).dtype
+        if self.pin is None or self.pin.numel() < total or self.pin.dtype != tdtype:
+            self.pin = torch.empty(total, dtype=tdtype, pin_memory=True)
+            self.free = None
+        if self.free is not None:
+            self.free.synchronize()  # the previous call's DMA has left the staging buffer (long done in practice)
+        host = self.pin.numpy()
+        off = 0
+        for a, k in zip(arrays, sizes):
+            host[off:off + k] = a.reshape(-1)
+            off += k
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.device)
+        main = torch.cuda.current_stream(self.device)
+        prev = self.which  # (the slot of the previous call: its readers are enqueued on `main` by now)
+        if self.dev[prev] is not None:
+            if self.used[prev] is None:
+                self.used[prev] = torch.cuda.Event()
+            self.used[prev].record(main)
+        self.which ^= 1
+        dev = self.dev[self.which]
+        if dev is None or dev.numel() < total or dev.dtype != tdtype:
+            dev = self.dev[self.which] = torch.empty(total, dtype=tdtype, device=self.device)
+        with torch.cuda.stream(self.stream):
+            if self.used[self.which] is not None:
+                self.stream.wait_event(self.used[self.which])
+            dev[:total].copy_(self.pin[:total], non_blocking=True)
+            self.free = torch.cuda.Event()
+            self.free.record(self.stream)
+        main.wait_event(self.free)
+        out, off = [], 0
+        for a, k in zip(arrays, sizes):
+            out.append(dev[off:off + k].view(a.shape))
+            off += k
+        return out
+
+
+class MI355XPreprocessingBatch:
+    """`Preprocessing.forward` (slam/preprocessing.py:269-290) for B frames at once, on the chain of
+    config/slam/preprocessing/grid_sample_mi355x.yaml: to_device_mi355x -> distortion_mi355x -> grid_sample_mi355x ->
+    to_tensor_mi355x.  `forward(dicts)` writes into every dict the keys, dtypes, shapes and values the four single filters
+    (`ToDevice`, `Distortion`, `GridSample`, `ToTensor`) write, bit for bit, including Distortion's pass-through (no
+    timestamps, `init_rpose` None or `activate: false`: `distorted` IS the uploaded float32 frame).
+
+    One upload per key for all B frames (one pinned buffer, one DMA), then ONE library call (`IcpBatch.preprocess`): two
+    launches de-skew the members with timestamps, four grid-sample all of them and write the float32 copy ToTensor makes.
+    `padded: true`: nothing is read back; `padded: false` (the yaml's default): the B sample counts are read with ONE
+    synchronisation and the dicts get V-row views (the exact-shape path's bits: same order of distinct voxel hashes).
+
+    Lifetime: the uploaded frames (`pc_device`, `timestamps_device`) follow ToDevice's rule — views of a device slot that
+    the call after next overwrites; clone them to keep them longer.  Every other tensor a call writes is a view of buffers
+    allocated by that call (kept alive by the views) and stays valid for as long as the caller holds it."""
+
+    CHAIN = ("to_device_mi355x", "distortion_mi355x", "grid_sample_mi355x", "to_tensor_mi355x")
+
+    def __init__(self, filters_config, count: int, device=None, batch: Optional[IcpBatch] = None):
+        cfg = filters_config
+        if isinstance(cfg, dict) and "filters" in cfg:
+            cfg = cfg["filters"]
+        if isinstance(cfg, dict):
+            cfg = [cfg[k] for k in sorted(cfg, key=lambda k: int(k))]
+        cfg = [dict(c) for c in cfg]
+        names = tuple(c.get("filter_name") for c in cfg)
+        assert_debug(names == self.CHAIN, f"MI355XPreprocessingBatch batches the chain {' -> '.join(self.CHAIN)} "
+                                          f"(config/slam/preprocessing/grid_sample_mi355x.yaml) only, got {' -> '.join(map(str, names))}")
+        try:
+            self.to_device = ToDeviceConfig(**cfg[0])
+            self.distortion = DistortionConfig(**cfg[1])
+            self.grid_sample = GridSampleConfig(**cfg[2])
+            self.to_tensor = ToTensorConfig(**cfg[3])
+        except TypeError as e:
+            raise AssertionError(f"MI355XPreprocessingBatch: unknown filter option ({e})") from None
+        dk = dict(self.to_device.keys)
+        by_target = {v: k for k, v in dk.items()}
+        c = self.distortion
+        assert_debug(c.pointcloud_key in by_target and set(dk.values()) <= {c.pointcloud_key, c.timestamps_key},
+                     "MI355XPreprocessingBatch: to_device_mi355x must upload exactly the frame (and its timestamps) "
+                     "distortion_mi355x reads")
+        assert_debug(self.grid_sample.pointcloud_key == c.output_key,
+                     "MI355XPreprocessingBatch: grid_sample_mi355x must sample distortion_mi355x's output")
+        assert_debug(dict(self.to_tensor.keys).keys() == {self.grid_sample.output_sample_key} and
+                     self.to_tensor.dtype == "float32",
+                     "MI355XPreprocessingBatch: to_tensor_mi355x must cast grid_sample_mi355x's samples to float32")
+        self._pc_src = by_target[c.pointcloud_key]
+        self._ts_src = by_target.get(c.timestamps_key)
+        dev = torch.device(device if device is not None and str(device) != "cpu" else self.to_device.device)
+        self.device = dev
+        self.count = int(count)
+        assert_debug(self.count >= 1, "a batch needs at least one frame")
+        if batch is None:
+            batch = IcpBatch([IcpContext(device=dev.index or 0) for _ in range(self.count)])
+        assert_debug(len(batch) == self.count, f"a batch of {len(batch)} contexts for {self.count} frames")
+        self.batch = batch
+        self._uploads = {k: _PackedUpload(dev) for k in dk}
+
+    def __len__(self):
+        return self.count
+
+    def forward(self, dicts):
+        assert_debug(len(dicts) == self.count, f"expected {self.count} frames, got {len(dicts)}")
+        c, gs = self.distortion, self.grid_sample
+        dev = self.device
+        # ---- ToDevice: every listed key present in the dicts, one DMA per key
+        for src, dst in dict(self.to_device.keys).items():
+            members = [k for k, d in enumerate(dicts) if src in d]
+            host, passed = [], []
+            for k in members:
+                a = dicts[k][src]
+                t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+                assert_debug(isinstance(t, torch.Tensor), f"cannot upload `{src}` of type {type(a)}")
+                (passed if t.is_cuda else host).append((k, t))
+            if host:
+                dtypes = {t.dtype for _, t in host}
+                assert_debug(len(dtypes) == 1, f"the `{src}` arrays of one batch must share a dtype, got {dtypes}")
+                for (k, _), v in zip(host, self._uploads[src]([t.numpy() for _, t in host])):
+                    dicts[k][dst] = v
+            for k, t in passed:
+                dicts[k][dst] = t.to(dev, non_blocking=True)
+        # ---- Distortion's decisions, GridSample's inputs
+        points, stamps, poses = [], [], []
+        for k, d in enumerate(dicts):
+            pc = d[c.pointcloud_key]
+            assert_debug(_is_device_tensor(pc) and pc.dtype == torch.float32 and pc.ndim == 2 and pc.shape[1] == 3,
+                         f"member {k}: expected a float32 [N, 3] frame, got {getattr(pc, 'dtype', type(pc))} "
+                         f"{tuple(getattr(pc, 'shape', ()))}")
+            no_distortion = not c.activate or (c.timestamps_key not in d)
+            no_distortion = no_distortion or (d[c.pose_key] is None if c.pose_key in d else False)
+            points.append(pc)
+            if no_distortion:
+                stamps.append(None)
+                poses.append(None)
+                continue
+            rpose = np.asarray(d[c.pose_key])
+            assert_debug(rpose.shape == (4, 4))
+            ts = d[c.timestamps_key]
+            assert_debug(isinstance(ts, torch.Tensor), f"member {k}: timestamps must be a tensor")
+            ts = ts.reshape(-1)
+            assert_debug(ts.shape[0] == pc.shape[0], f"member {k}: {ts.shape[0]} timestamps for {pc.shape[0]} points")
+            stamps.append(ts.to(dev, torch.float64).contiguous())
+            poses.append(rpose)
+        # ---- the outputs of all members in four allocations
+        ns = [int(p.shape[0]) for p in points]
+        n64 = sum(n for n, t in zip(ns, stamps) if t is not None)
+        buf64 = torch.empty(6 * n64, dtype=torch.float64, device=dev)
+        buf32 = torch.empty(3 * sum(ns), dtype=torch.float32, device=dev)
+        bufi = torch.empty(sum(ns), dtype=torch.int64, device=dev)
+        counts = torch.empty(self.count, dtype=torch.int32, device=dev)
+        outs, o64, o = [], 0, 0
+        for k, (n, t) in enumerate(zip(ns, stamps)):
+            f32 = buf32[3 * o:3 * (o + n)].view(n, 3)
+            e = {"samples_f32": f32, "indices": bufi[o:o + n], "count": counts[k], "distorted": None, "samples": f32}
+            if t is not None:
+                e["distorted"] = buf64[3 * o64:3 * (o64 + n)].view(n, 3)
+                e["samples"] = buf64[3 * (n64 + o64):3 * (n64 + o64 + n)].view(n, 3)
+                o64 += n
+            o += n
+            outs.append(e)
+        self.batch.preprocess(points, stamps, poses, gs.voxel_size, out=outs)
+        padded = bool(getattr(gs, "padded", False))
+        v = counts.cpu().tolist() if not padded else None  # (padded false: ONE synchronisation for the batch)
+        (sample_src, sample_dst), = dict(self.to_tensor.keys).items()
+        for k, (d, e) in enumerate(zip(dicts, outs)):
+            d[c.output_key] = e["distorted"] if e["distorted"] is not None else points[k]
+            if padded:
+                d[gs.output_sample_key] = e["samples"]
+                d[gs.output_indices_key] = e["indices"]
+                d[getattr(gs, "output_count_key", "sample_count")] = e["count"]
+                d[sample_dst] = e["samples_f32"]
+            else:
+                d[gs.output_sample_key] = e["samples"][:v[k]]
+                d[gs.output_indices_key] = e["indices"][:v[k]]
+                d[sample_dst] = e["samples_f32"][:v[k]] if e["samples"] is not e["samples_f32"] else d[gs.output_sample_key]
+        return dicts
+
+    __call__ = forward
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -842,7 +1039,9 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         return np.asarray(rpose).astype(np.float32).reshape(-1)[-16:].reshape(4, 4)
 
     # ------------------------------------------------------------------------------------------------------------------
-    def _read_input(self, data_dict: dict):  # :319-358
+    def _read_input(self, data_dict: dict, projected=None):  # :319-358
+        """`projected`: (vertex map, rows or None) of this frame's [N, 3] device rows, already enqueued by the caller
+        (`MI355XICPFrameToModelBatch`: one batched projection for all members) — the projection is not repeated here."""
         key = self.config.data_key
         assert_debug(key in data_dict, f"Could not find the key `{key}` in the input dictionary.\n"
                                        f"With keys : {data_dict.keys()}). Set the parameter "
@@ -875,7 +1074,9 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
             else:
                 assert_debug(data.ndim == 2)
                 pc = data.to(self.device, torch.float32).contiguous()
-                if not self._sample_pointcloud and pc.is_cuda and hasattr(self.ctx, "project_rows"):
+                if projected is not None:
+                    vmap, self._tgt_rows = projected
+                elif not self._sample_pointcloud and pc.is_cuda and hasattr(self.ctx, "project_rows"):
                     # the targets will be the pixels of this vertex map (sample_points): the projection writes them as
                     # rows too, instead of a transposing copy per frame
                     vmap, self._tgt_rows = self.ctx.project_rows(pc)
@@ -1076,13 +1277,16 @@ class MI355XICPFrameToModelBatch:
     same frames (ICPFrameToModel.do_process_next_frame, slam/odometry/icp_odometry.py:157-246; __update_map :360-380).
 
     kd-tree style map (kdtree_local_map / hashgrid_local_map): one launch per ICP iteration for all B registrations and
-    one `map_update_staged` — key-frame insertion, eviction, grid rebuild and eager normals.  Per member still: the
-    projection, the staging of the frame's rows and the frame-0 insertion of the vertex map.
+    one `map_update_staged` — key-frame insertion, eviction, grid rebuild and eager normals; the frames' rows are staged by
+    one `stage` call (two launches).  Per member still: the frame-0 insertion of the vertex map.
 
     Projective map (projective_local_map, local_map.py:91-240): frame 0 is one batched insertion; every later frame is one
     `pmap_register_launch` (three launches per ICP iteration for all B, every iteration enqueued) and one `pmap_update`
-    (four launches: the vertex maps of the members that take a key frame, the model rebuild of every member).  Per member
-    still: `_read_input` (the projection of an [N,3] frame).
+    (four launches: the vertex maps of the members that take a key frame, the model rebuild of every member).
+
+    Both maps: [N,3] device frames are projected by ONE `project_rows` call (two launches) for all members; the rest of
+    `_read_input` runs per member.  [3,H,W] / [1,3,H,W] vertex maps take `_read_input` per member.  `MI355XPreprocessingBatch`
+    prepares the B frames in front of it in one call.
 
     Input: torch tensors (device-resident preprocessing, or [3,H,W] / [1,3,H,W] vertex maps)."""
 
@@ -1130,8 +1334,17 @@ class MI355XICPFrameToModelBatch:
             assert_debug(isinstance(d[key], torch.Tensor),
                          "MI355XICPFrameToModelBatch takes torch tensors (device-resident preprocessing), not numpy input")
         self.batch.use_torch_stream()
-        for m, d in zip(members, data_dicts):
-            m._read_input(d)  # the projection, per member
+        frames = [d[key] for d in data_dicts]
+        if all(f.ndim == 2 and f.is_cuda for f in frames):
+            # [N, 3] device frames: ONE projection call for all members (two launches), rows where a member's targets are
+            # the pixels of its vertex map (sample_points), the rest of _read_input per member
+            pcs = [f.to(self.device, torch.float32).contiguous() for f in frames]
+            projected = self.batch.project_rows(pcs, rows=[not m._sample_pointcloud for m in members])
+            for m, d, pr in zip(members, data_dicts, projected):
+                m._read_input(d, projected=pr)
+        else:
+            for m, d in zip(members, data_dicts):
+                m._read_input(d)  # vertex maps: as the single plugin
         if members[0]._projective:
             self._process_projective(data_dicts)
             return
