@@ -464,7 +464,23 @@ int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
  *                              chunks from icp_batch_register_end while a member is still running — a member whose loop has
  *                              ended idles on the device.  While the batch holds iterations back its members refuse the
  *                              single-context entry points (ICP_ERR_INVALID_ARGUMENT).  Point-to-plane registrations on the
- *                              fused path only (eager normals, no exchange, no profiling): ICP_ERR_INVALID_ARGUMENT otherwise;
+ *                              fused path only (eager normals, no exchange, no profiling): ICP_ERR_INVALID_ARGUMENT otherwise.
+ *                              SHARED OPTIONS: one launch runs one kernel instantiation for all members and one host loop
+ *                              decides how many iterations go onto the stream, so besides the stream, max_num_alignments,
+ *                              scheme and sigma the members must have EQUAL values of threshold_delta_pose (equal, not only
+ *                              both zero or both live: the chunks are sized for one stop test) and of the options
+ *                              chunked_launch, lead_after_dense, hit_records, late_from, late_waves, wide_until, narrow_from,
+ *                              nn_cache and ball_search.  A difference is refused before any member changes
+ *                              (ICP_ERR_INVALID_ARGUMENT, icp_batch_last_error names the option; no scan imported, no map or
+ *                              pose touched, nothing enqueued: every member registers on its own afterwards as if the call
+ *                              had not been made).  Every other option is the member's own and travels in its descriptor: the
+ *                              ball / far search options (ball_lanes, ball_empty, ball_max, far_lanes, far_min, far_max),
+ *                              wave_misses, refresh_at, refresh_margin, frame_seed, xcd_sectors and everything that steers the
+ *                              map update (carry_normals, normals_list, knn_lanes, cell_lists) may differ from member to
+ *                              member; lead launches run when every member allows them (lead_solve).  A launch that fails
+ *                              after the checks (a member that cannot take the fused path, a HIP error) gives the
+ *                              registration up: no member stays in registration or held by the batch.
+ *                              icp_batch_pmap_register_launch applies the same rule;
  *   icp_batch_project          icp_project for every member in two launches: xyz[b] [n[b],3] -> vmap_out[b] [3,H,W] of member b
  *                              (Projector.build_projection_map, slam/common/projection.py:331-418, as ICPFrameToModel._read_input
  *                              calls it per frame, icp_odometry.py:333); DEVICE pointers only;

@@ -2035,6 +2035,19 @@ static int batch_fail(icp_batch* b, int code, const std::string& msg) {
     return code;
 }
 
+// a batched registration that could not be enqueued to its end is given up: nothing is held back any more, no member is "in
+// registration" or refuses the single-context entry points
+static void batch_abandon(icp_batch* b) {
+    b->run_active = false;
+    b->run_next = b->run_iters;
+    for (icp_ctx* ctx : b->members) {
+        ctx->batch_hold = false;
+        ctx->in_registration = false;
+        ctx->result_fold_to = nullptr;
+        ctx->result_folded = false;
+    }
+}
+
 int icp_batch_create(icp_ctx* const* ctxs, int32_t count, icp_batch** out) {
     if (!ctxs || !out || count < 1 || count > ICP_BATCH_MAX_SEQUENCES) return ICP_ERR_INVALID_ARGUMENT;
     *out = nullptr;
@@ -2199,9 +2212,38 @@ static int batch_enqueue(icp_batch* b, int chunk, const PackDesc* packs, bool fi
 static int batch_flush(icp_batch* b) {
     if (!b->run_active) return ICP_OK;
     const int rc = batch_enqueue(b, -1, nullptr, false);
+    if (rc) batch_abandon(b);
     b->run_active = false;
     for (icp_ctx* ctx : b->members) ctx->batch_hold = false;
     return rc;
+}
+
+// What batch_enqueue, prepare_iterate_batch and launch_iterate_batch read from ONE member on behalf of all (the stop
+// threshold and "chunked_launch": how many iterations a chunk holds; "lead_after_dense", "wide_until", "narrow_from",
+// "nn_cache", "ball_search", "late_from": which shape an iteration runs in and which launch solves it; "hit_records",
+// "late_waves": which instantiation is launched) must be equal across the members: include/icp_mi355x.h,
+// icp_batch_register_launch.  Checked before any member changes; the message names the option.  Everything else travels in
+// the member's own descriptor.
+static int batch_shared_options_check(icp_batch* b, const char* what) {
+    const icp_ctx* first = b->members[0];
+    for (size_t i = 1; i < b->members.size(); ++i) {
+        const icp_ctx* ctx = b->members[i];
+        const char* name = nullptr;
+        if (ctx->cfg.threshold_delta_pose != first->cfg.threshold_delta_pose) name = "threshold_delta_pose";
+        else if (ctx->chunked_launch != first->chunked_launch) name = "chunked_launch";
+        else if (ctx->lead_after_dense != first->lead_after_dense) name = "lead_after_dense";
+        else if (ctx->hit_records != first->hit_records) name = "hit_records";
+        else if (ctx->late_from != first->late_from) name = "late_from";
+        else if (ctx->late_waves != first->late_waves) name = "late_waves";
+        else if (ctx->wide_until != first->wide_until) name = "wide_until";
+        else if (ctx->narrow_from != first->narrow_from) name = "narrow_from";
+        else if (ctx->use_nn_cache != first->use_nn_cache) name = "nn_cache";
+        else if (ctx->ball_search != first->ball_search) name = "ball_search";
+        if (name)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, std::string(what) + ", member " + std::to_string(i) + ": the members must share \"" +
+                                                              name + "\" (it differs from member 0's; nothing was changed)");
+    }
+    return ICP_OK;
 }
 
 int icp_batch_register_launch(icp_batch* b, const float* const* xyz, const int64_t* n, int mem, int target_mode,
@@ -2224,17 +2266,15 @@ int icp_batch_register_launch(icp_batch* b, const float* const* xyz, const int64
             return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched registration: point-to-plane registrations without exchange, "
                                                           "profiling or search statistics only");
     }
-    struct Unwind {  // an error below leaves no member "in registration" (and none counted among the registering contexts)
-        icp_batch* b;
+    if (int rc_options = batch_shared_options_check(b, "batched registration")) return rc_options;
+    struct Unwind {  // an error below leaves no member "in registration" (and none counted among the registering contexts),
+        icp_batch* b;  // nothing held back by the batch and no member refusing the single-context entry points
         bool armed = true;
         ~Unwind() {
             if (!armed) return;
-            for (icp_ctx* ctx : b->members) {
-                ctx->in_registration = false;
-                ctx->result_fold_to = nullptr;
-                ctx->result_folded = false;
+            batch_abandon(b);
+            for (icp_ctx* ctx : b->members)
                 if (ctx->r_count == 0) registering_leave(ctx);
-            }
         }
     } unwind{b};
     int rc = ICP_OK;
@@ -2645,6 +2685,7 @@ int icp_batch_pmap_register_launch(icp_batch* b, const float* const* xyz, const 
     // ---- every member is checked before any member changes
     int rc = pmap_batch_check(b, "batched projective registration");
     if (rc) return rc;
+    if ((rc = batch_shared_options_check(b, "batched projective registration"))) return rc;
     int max_n = 0;
     for (int i = 0; i < count; ++i) {
         icp_ctx* ctx = ctxs[i];
@@ -2659,16 +2700,11 @@ int icp_batch_pmap_register_launch(icp_batch* b, const float* const* xyz, const 
             return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "no previous registration to start from");
         max_n = std::max(max_n, (int)n[i]);
     }
-    struct Unwind {  // an error below leaves no member "in registration"
+    struct Unwind {  // an error below leaves no member "in registration" or held by the batch
         icp_batch* b;
         bool armed = true;
         ~Unwind() {
-            if (!armed) return;
-            for (icp_ctx* ctx : b->members) {
-                ctx->in_registration = false;
-                ctx->result_fold_to = nullptr;
-                ctx->result_folded = false;
-            }
+            if (armed) batch_abandon(b);
         }
     } unwind{b};
     // ---- descriptor slot: [packs | registrations | sum + solve | sum + solve of the last iteration]
@@ -2844,7 +2880,10 @@ int icp_batch_register_end(icp_batch* b, icp_register_result* results, double* l
             break;
         }
         const int rc_chunk = batch_enqueue(b, 4, nullptr, false);
-        if (rc_chunk) return rc_chunk;
+        if (rc_chunk) {
+            batch_abandon(b);
+            return rc_chunk;
+        }
     }
     for (icp_ctx* ctx : b->members) ctx->batch_hold = false;
     int first_rc = ICP_OK;
@@ -2853,6 +2892,7 @@ int icp_batch_register_end(icp_batch* b, icp_register_result* results, double* l
         icp_ctx* ctx = b->members[i];
         const int rc = icp_register_end(ctx, &results[i], loss_per_iter_out ? loss_per_iter_out + i * cap : nullptr,
                                         dx_per_iter_out ? dx_per_iter_out + i * cap * 6 : nullptr);
+        if (rc) results[i].status = rc;  // (whatever ended this member: a caller tells the healthy members by their status)
         if (rc && !first_rc) {
             first_rc = rc;
             b->error = ctx->error;

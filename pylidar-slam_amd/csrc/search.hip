@@ -4415,7 +4415,8 @@ int launch_iterate_fused(icp_ctx* ctx, int* rows_out, int* quad_out, bool lead_m
 // ---- the batched launch: one fused iteration of every member's registration (api.hip: icp_batch_*) ---------------------
 // `table_host` / `table_dev`: room for `count` descriptors (pinned host memory the caller copies to the device in front of
 // the launches of the frame; the launch reads table_dev).  All members must come out with the same instantiation (same
-// options, same iteration index): anything else is refused — the caller then falls back to one launch per member.
+// options, same iteration index: icp_batch_register_launch checks the shared options before any member changes,
+// api.hip: batch_shared_options_check): anything else is refused — the caller then gives the registration up.
 int prepare_iterate_batch(icp_ctx* const* ctxs, int count, bool lead_mode, const int* prev_rows, const int* prev_quad,
                           void* table_host, BatchedIteration* out) {
     IterateDesc* table = reinterpret_cast<IterateDesc*>(table_host);
@@ -4430,7 +4431,7 @@ int prepare_iterate_batch(icp_ctx* const* ctxs, int count, bool lead_mode, const
             return ICP_ERR_INVALID_ARGUMENT;
         }
         out->shape = (int)fl.shape;
-        out->records = fl.d.in.rec != nullptr ? 1 : 0;  // (same options in every member: checked by the caller)
+        out->records = fl.d.in.rec != nullptr ? 1 : 0;  // ("hit_records" is equal across the members: batch_shared_options_check)
         out->rows[b] = fl.rows;
         out->quad[b] = fl.quad;
         table[b] = fl.d;

@@ -1030,20 +1030,34 @@ class IcpBatch:
         self._check(self._lib.icp_batch_pmap_update(self._h, rel.ctypes.data, vm, mem, int(normals_kernel_size)))
 
     def register_end(self):
-        """One wait for all members; a list of `RegisterResult`s (raises what the first failing member would raise)."""
+        """One wait for all members; a list of `RegisterResult`s.  Raises what the first failing member would raise; the
+        library has collected every member all the same, so the exception carries `.results` (the list, None at the
+        failing positions) and `.failed` (their indices): a neighbour's singular system costs the healthy members
+        nothing."""
         b = len(self.contexts)
         cap = max(1, int(self.contexts[0].config.max_num_alignments))
         res = (IcpRegisterResult * b)()
+        for r in res:
+            r.status = _lib.ICP_ERR_INVALID_ARGUMENT  # (a slot the library never reached is no result)
         losses = (C.c_double * (cap * b))()
         dxs = (C.c_float * (6 * cap * b))()
         rc = self._lib.icp_batch_register_end(self._h, res, losses, dxs)
-        self._check(rc)
         la = np.array(losses, np.float64).reshape(b, cap)
         da = np.array(dxs, np.float32).reshape(b, cap, 6)
         out = []
         for i in range(b):
+            if rc != 0 and int(res[i].status) != 0:
+                out.append(None)
+                continue
             k = int(res[i].iterations)
             out.append(RegisterResult(np.array(res[i].pose, np.float32).reshape(4, 4), np.array(res[i].params, np.float32), k,
                                       bool(res[i].converged), int(res[i].num_targets), int(res[i].normals_computed),
                                       la[i, :k].copy(), da[i, :k].copy()))
+        if rc != 0:
+            try:
+                self._check(rc)
+            except Exception as err:
+                err.results = out
+                err.failed = [i for i, r in enumerate(out) if r is None]
+                raise
         return out

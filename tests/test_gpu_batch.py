@@ -4,6 +4,8 @@ body on the single launch's arguments (read from a descriptor table instead of t
 
 Reference semantics per sequence: ICPFrameToModel.register_new_frame (slam/odometry/icp_odometry.py:248-299) followed by
 the pose-only branch of __update_map (:379)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -59,12 +61,20 @@ def _run_single(kw, options, seq, frames, init_mode, device=None, sync_order=Fal
     return out, mp, fb
 
 
+def _member_options(options, count):
+    """`options`: one dict for every member, or a list with one dict per member."""
+    if isinstance(options, dict):
+        return [options] * count
+    assert len(options) == count
+    return list(options)
+
+
 def _run_batch(kw, options, seqs, frames, init_mode, device=None, lengths=None, sync_order=False):
     from pylidar_slam_amd.engine import IcpBatch
     ctxs = []
-    for scans, model in seqs:
+    for (scans, model), opts in zip(seqs, _member_options(options, len(seqs))):
         ctx = _ctx(**kw)
-        for k, v in options.items():
+        for k, v in opts.items():
             ctx.set_option(k, v)
         ctx.map_set(device.from_numpy(model).cuda() if device is not None else model)
         ctxs.append(ctx)
@@ -106,9 +116,23 @@ def _assert_same(single, batched, tag):
     assert np.array_equal(mp_s, mp_b), tag
 
 
+BENCH_OPTIONS = {"wide_until": 0, "cell_lists": 1}  # bench.py's `leg_options`: what the batched leg of the benchmark runs
+
+
+def _without_cell_lists(options):
+    return dict(options, cell_lists=0)
+
+
+@functools.lru_cache(maxsize=None)
+def _benchmark_sequences():
+    """Four 64x2048 drives against 100 000-point maps (BASELINE configs[1] sizes), generated once per session: the scene
+    generator on the CPU is the expensive part of every test at this size."""
+    return tuple(_sequences(4, 64, 2048, 100_000, 3, seed0=4321, map_scans=8))
+
+
 @pytest.mark.parametrize("variant", ["default", "no_lead", "narrow_only", "live_threshold", "from_last", "host_arrays",
                                      "ragged", "hit_records", "late_kernel", "live_threshold_pose_first",
-                                     "many_iterations_pose_first"])
+                                     "many_iterations_pose_first", "cell_lists", "bench_options", "mixed_cell_lists"])
 def test_batched_registration_equals_single_sequences(torch_cuda, variant):
     """Three sequences with different scenes, four chained frames each (registration from the previous pose, pose-only map
     update by the device-resident pose): batched vs every sequence alone on a context of its own — poses, parameters,
@@ -117,7 +141,11 @@ def test_batched_registration_equals_single_sequences(torch_cuda, variant):
     threshold (members stop after different numbers of iterations: a finished member idles on the device), the initial
     guess read on the device, host arrays in, scans of different lengths in one batch, hit records and the late kernel (both
     off by default), and the plugin's order — poses first, then the maps — with a live threshold: the batch enqueues a first
-    chunk of iterations and further chunks from `register_end` while a member is still running."""
+    chunk of iterations and further chunks from `register_end` while a member is still running.  The cell lists of the grid
+    build ("cell_lists", off by default, ON in the benchmark's batched leg): on for every member, the benchmark's exact
+    option set, and members 0 and 2 on lists beside member 1 off (one batched build then runs the list scan AND the table
+    scan, each kernel skipping the other's members) — there every member must also equal, bit for bit, the same member
+    with "cell_lists" 0: it is a pure schedule option (test_schedule_options_are_bit_identical)."""
     kw = dict(height=32, width=1024, max_num_alignments=12, threshold_delta_pose=0.0, scheme="geman_mcclure", sigma=0.3)
     options, init_mode, device, lengths, sync_order = {}, "pose", torch_cuda, None, False
     if variant == "no_lead":
@@ -145,30 +173,47 @@ def test_batched_registration_equals_single_sequences(torch_cuda, variant):
         options = {"hit_records": 1}
     elif variant == "late_kernel":  # (the late kernel from the third launch on, batched: k_iterate_late_batch)
         options = {"hit_records": 1, "late_from": 2, "wide_until": 0}
+    elif variant == "cell_lists":
+        options = {"cell_lists": 1}
+    elif variant == "bench_options":
+        options = dict(BENCH_OPTIONS)
+    elif variant == "mixed_cell_lists":
+        options = [{"cell_lists": 1}, {"cell_lists": 0}, {"cell_lists": 1}]
     seqs = _sequences(3, 32, 1024, 30_000, 4)
     if lengths is not None:
         seqs = [([s[:lengths[b]] for s in sc], m) for b, (sc, m) in enumerate(seqs)]
     batched = _run_batch(kw, options, seqs, 4, init_mode, device, sync_order=sync_order)
-    for b, seq in enumerate(seqs):
-        single = _run_single(kw, options, seq, 4, init_mode, device, sync_order=sync_order)
+    for b, (seq, opts) in enumerate(zip(seqs, _member_options(options, 3))):
+        single = _run_single(kw, opts, seq, 4, init_mode, device, sync_order=sync_order)
         _assert_same(single, ([r for r in batched[0][b]], batched[1][b], batched[2][b]), (variant, b))
+        if variant in ("cell_lists", "bench_options", "mixed_cell_lists"):  # lists == no lists, to the bit
+            plain = _run_single(kw, _without_cell_lists(opts), seq, 4, init_mode, device, sync_order=sync_order)
+            _assert_same(plain, single, (variant, b, "cell_lists 1 vs 0"))
+            _assert_same(plain, ([r for r in batched[0][b]], batched[1][b], batched[2][b]), (variant, b, "batched vs cell_lists 0"))
     if variant in ("live_threshold", "live_threshold_pose_first", "many_iterations_pose_first"):
         its = [[r.iterations for r in batched[0][b]] for b in range(3)]
         assert any(i < kw["max_num_alignments"] for row in its for i in row), its  # (the threshold did fire: members went idle inside the batch)
 
 
-def test_batched_registration_at_benchmark_size(torch_cuda):
+@pytest.mark.parametrize("variant", ["default", "bench_options"])
+def test_batched_registration_at_benchmark_size(torch_cuda, variant):
     """BASELINE configs[1] sizes (64x2048 scans against 100 000-point maps, 20 forced iterations), four sequences per
     launch, three chained frames: bit-equal to the four sequences run alone, and every pose within 1e-4 m / 1e-4 rad of
     the generator's ground truth motion is NOT asserted here (noise-limited: the C2 parity test pins the pose on the
-    reference) — this test pins batched == single."""
+    reference) — this test pins batched == single.  `bench_options`: the option set of the benchmark's batched leg
+    (512-thread shape from the first iteration, cell lists in the grid build) — and there every member also equals the
+    same member without cell lists, bit for bit."""
     kw = dict(height=64, width=2048, max_num_alignments=20, threshold_delta_pose=0.0, scheme="geman_mcclure", sigma=0.3)
-    seqs = _sequences(4, 64, 2048, 100_000, 3, seed0=4321, map_scans=8)
-    batched = _run_batch(kw, {}, seqs, 3, "pose", torch_cuda)
+    options = dict(BENCH_OPTIONS) if variant == "bench_options" else {}
+    seqs = list(_benchmark_sequences())
+    batched = _run_batch(kw, options, seqs, 3, "pose", torch_cuda)
     for b, seq in enumerate(seqs):
-        single = _run_single(kw, {}, seq, 3, "pose", torch_cuda)
-        _assert_same(single, ([r for r in batched[0][b]], batched[1][b], batched[2][b]), ("c2", b))
+        single = _run_single(kw, options, seq, 3, "pose", torch_cuda)
+        _assert_same(single, ([r for r in batched[0][b]], batched[1][b], batched[2][b]), ("c2", variant, b))
         assert all(r.iterations == 20 for r in batched[0][b])
+        if variant == "bench_options":
+            plain = _run_single(kw, _without_cell_lists(options), seq, 3, "pose", torch_cuda)
+            _assert_same(plain, single, ("c2", b, "cell_lists 1 vs 0"))
 
 
 def test_batch_refuses_what_it_cannot_run(torch_cuda):

@@ -53,9 +53,10 @@ def _record(res):
     return (res.pose.copy(), int(res.iterations), res.losses.copy(), res.dx.copy())
 
 
-def _run_single(torch, scans, cfg, options):
+def _run_single(torch, scans, cfg, options, probe=None):
     """The sequence through MI355XICPFrameToModel alone (device-resident preprocessing): per frame (pose, iterations,
-    losses, steps), the map, the window size and the plugin's trajectory."""
+    losses, steps), the map, the window size and the plugin's trajectory.  `probe(0, ctx, f)`: called on the live
+    context behind every registered frame f (the update of the map by that frame included)."""
     from pylidar_slam_amd import odometry as our
     dev = torch.device("cuda:0")
     odo = our.MI355XICPFrameToModel(cfg, projector=our.SphericalProjector(H, W), device=dev)
@@ -76,13 +77,16 @@ def _run_single(torch, scans, cfg, options):
             init.save_real_motion(d["odometry_pose"], d)
             assert np.array_equal(d["odometry_pose"], odo.last_result.pose)
             out.append(_record(odo.last_result))
+            if probe is not None:
+                probe(0, odo.ctx, f)
     result = (out, odo.ctx.map_points(), odo.ctx.map_num_clouds(), odo.get_relative_poses())
     odo.ctx.close()
     return result
 
 
-def _run_batch(torch, sequences, cfg, options):
-    """The same sequences through MI355XICPFrameToModelBatch: per member what _run_single returns."""
+def _run_batch(torch, sequences, cfg, options, probe=None):
+    """The same sequences through MI355XICPFrameToModelBatch: per member what _run_single returns.  `probe(b, ctx, f)`:
+    called on every member's live context behind every registered frame f."""
     from pylidar_slam_amd import odometry as our
     dev = torch.device("cuda:0")
     count = len(sequences)
@@ -114,6 +118,9 @@ def _run_batch(torch, sequences, cfg, options):
             res = odo.members[b].last_result
             assert np.array_equal(d["odometry_pose"], res.pose)
             out[b].append(_record(res))
+        if probe is not None:
+            for b in range(count):
+                probe(b, odo.members[b].ctx, f)
     result = [(out[b], odo.members[b].ctx.map_points(), odo.members[b].ctx.map_num_clouds(), odo.get_relative_poses(b))
               for b in range(count)]
     odo.batch.close()
