@@ -1151,7 +1151,12 @@ def test_projective_components(torch_cuda, O, golden_projective):
     nm = ctx.compute_normal_map(vm[0], 5)
     exact = O.compute_normal_map(vm[0], 5, dtype=np.float64)
     both = (np.abs(nm).max(axis=0) > 0) & (np.abs(exact).max(axis=0) > 0)
-    assert ((np.abs(nm).max(axis=0) > 0) == (np.abs(exact).max(axis=0) > 0)).mean() > 0.999
+    # every pixel accounted for (tests/projective_cases.py): null -> 0, determined -> the oracle's zero / non-zero status and
+    # its direction within the derived tolerance; this map has no undetermined pixel
+    import projective_cases as PC
+    account = PC.NormalReference(vm[0], 5).account(nm)
+    assert len(account["unexplained"]) == 0 and account["undetermined"] == 0, account
+    assert np.array_equal(np.abs(nm).max(axis=0) > 0, np.abs(exact).max(axis=0) > 0)
     ang = np.linalg.norm(np.cross(nm, exact, axis=0), axis=0)[both]  # sin(angle): well conditioned near 0
     assert ang.max() < 1e-4 and np.median(ang) < 1e-6, (ang.max(), np.median(ang))
     ref_n = g["nmap0"]
@@ -1175,22 +1180,38 @@ def test_projective_map_model_and_search(torch_cuda, O, golden_projective):
         orc.update(pose, v)
         assert ctx.pmap_num_maps() == len(orc.vmaps)
     mv, mn = ctx.pmap_model()
-    # the model maps: same pixels occupied, same points (f32 transform rounding), normals within the f64-vs-f32 rounding
+    # the model maps, every pixel of every layer (tests/projective_cases.py): the oracle's winner and its point within the
+    # float32 transform rounding, or explained as a coin toss of the reference's own projection / a z-buffer tie.  The
+    # oracle composes its window poses as the library does and stores the device's normal maps, so the model normals are
+    # held bit for bit.
+    import projective_cases as PC
+    lib = PC.LibraryWindowOracle(h, w, 3.0, -24.0, local_map_size=2, nmap_of=lambda v: ctx.compute_normal_map(v, 5))
+    for pose, v in [(np.eye(4, dtype=np.float32), vm[0]), (rel, vm[1]), (rel, None), (rel, vm[2])]:
+        lib.update(pose, v)
+    for a, b in zip(lib.poses, orc.poses):
+        assert np.abs(a - b).max() <= PC.pose_drift_bound(3, max(np.abs(a).max(), np.abs(b).max()))
+    model = PC.account_model(mv, mn, lib.vmaps, lib.nmaps, lib.poses, h, w)
+    assert model["unexplained"] == [], model["unexplained"][:8]
+    assert model["explained"] <= 0.005 * model["occupied"]
     occ = np.abs(mv).max(axis=1) > 0
-    assert (occ == (np.abs(orc.model_vmap).max(axis=1) > 0)).mean() > 0.9995
+    assert (occ != (np.abs(orc.model_vmap).max(axis=1) > 0)).sum() <= 2 * model["explained"]
     same = occ & (np.abs(orc.model_vmap).max(axis=1) > 0)
     dv = np.abs(mv - orc.model_vmap).max(axis=1)[same]
-    assert np.percentile(dv, 99.9) < 1e-4, np.percentile(dv, 99.9)  # a few pixels pick another z-buffer winner
-    # association of a transformed scan
+    assert (dv >= 1e-4).sum() <= model["explained"], ((dv >= 1e-4).sum(), model["explained"])
+    # association of a transformed scan: every row the argmin layer of the device's own model at the device's own pixel,
+    # the matched targets the oracle's apart from explained coin tosses — unconditionally
     pts = O.apply_transformation(O.vertex_map_to_points(vm[3]), rel)
     pts = pts[np.abs(pts).max(axis=1) > 0]
     nb, nm, tg = ctx.pmap_nearest_neighbor_search(pts)
+    _, index = ctx.project(pts, with_index=True)
+    got = PC.account_association((nb, nm, tg), mv, mn, pts, index, lib.nearest_neighbor_search(pts),
+                                 model["explained_pixels"])
+    assert got["unexplained"] == [], got["unexplained"][:8]
+    assert got["rows"] == got["expected_rows"] and got["explained"] <= max(3, got["rows"] // 2000)
     onb, onm, otg = orc.nearest_neighbor_search(pts)
     assert abs(nb.shape[0] - onb.shape[0]) <= max(3, onb.shape[0] // 2000)
-    if nb.shape[0] == onb.shape[0]:
-        close = np.abs(nb - onb).max(axis=1) < 1e-4
-        assert close.mean() > 0.998
-        np.testing.assert_array_equal(tg, otg)
+    print(f"projective model: explained {model['explained']} of {model['occupied']}; association: {got['rows']} rows, "
+          f"explained {got['explained']}")
 
 
 @pytest.mark.parametrize("run", ["ls", "nbh"])
