@@ -20,7 +20,10 @@ _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device in
 
 
 class InvalidJacobianError(RuntimeError):
-    """RuntimeError("Invalid Jacobian in Gauss Newton minimization") of slam/common/optimization.py:336."""
+    """RuntimeError("Invalid Jacobian in Gauss Newton minimization") of slam/common/optimization.py:336.  Raised by a
+    registration it carries `result`: the RegisterResult up to and including the failing iteration (the library fills the
+    result block and the histories before it returns the status)."""
+    result = None
 
 
 class ExchangeTimeoutError(RuntimeError):
@@ -609,6 +612,13 @@ class IcpContext:
                               bool(res.converged), int(res.num_targets), int(res.normals_computed),
                               np.array(losses[:k], np.float64), np.array(dxs, np.float32).reshape(-1, 6)[:k])
 
+    def _check_registration(self, rc: int, res: IcpRegisterResult, losses, dxs):
+        try:
+            self._check(rc)
+        except InvalidJacobianError as e:
+            e.result = self._result(res, losses, dxs)
+            raise
+
     def register(self, points: Array, init_pose=None, skip_null: bool = False) -> RegisterResult:
         self._bind(points)
         p, mem, keep = _ptr_mem(points)
@@ -618,8 +628,8 @@ class IcpContext:
         dxs = (C.c_float * (6 * cap))()
         res = IcpRegisterResult()
         init = _pose16(init_pose if init_pose is not None else np.eye(4))
-        self._check(self._lib.icp_register(self._h, p, n, mem, TARGETS_SKIP_NULL if skip_null else TARGETS_ALL, init,
-                                           C.byref(res), losses, dxs))
+        self._check_registration(self._lib.icp_register(self._h, p, n, mem, TARGETS_SKIP_NULL if skip_null else TARGETS_ALL,
+                                                        init, C.byref(res), losses, dxs), res, losses, dxs)
         return self._result(res, losses, dxs)
 
     # ---- multi-GPU: exchange of the normal equations inside the library ----------------------------------------------
@@ -700,7 +710,7 @@ class IcpContext:
         losses = (C.c_double * cap)()
         dxs = (C.c_float * (6 * cap))()
         res = IcpRegisterResult()
-        self._check(self._lib.icp_register_end(self._h, C.byref(res), losses, dxs))
+        self._check_registration(self._lib.icp_register_end(self._h, C.byref(res), losses, dxs), res, losses, dxs)
         return self._result(res, losses, dxs)
 
     def raise_for_status(self, rc: int):

@@ -856,12 +856,10 @@ def test_async_register_and_device_pose_map_update_are_bit_identical(torch_cuda,
 
 
 def _c2_inputs():
-    """Scan / map pair of the C2 parity tests (the inputs oracle/make_golden_c2.py ran the reference on)."""
-    from pylidar_slam_amd.synthetic import SceneConfig, make_fixed_map, make_sequence
-    cfg = SceneConfig(height=64, width=2048)
-    scans, poses = make_sequence(cfg, 9)
-    model = make_fixed_map(cfg, scans[:8], poses[:8], ref_frame=7, num_points=100_000)
-    return scans[8], model
+    """Scan / map pair of the C2 parity tests (shared: tests/iteration_audit.py)."""
+    from iteration_audit import c2_inputs
+    scan, model = c2_inputs()
+    return scan.copy(), model.copy()
 
 
 def test_c2_full_size_registration_vs_reference_and_oracle(torch_cuda, O):
@@ -916,16 +914,10 @@ def test_c2_full_size_registration_vs_reference_and_oracle(torch_cuda, O):
 
 
 def _bench_workload():
-    """bench.py's headline workload (`make_workload(0, "pingpong")`): tracked scans the map has never seen, the map the
-    voxel-subsampled union of eight OTHER scans — restated here so that the test does not import the benchmark."""
-    from pylidar_slam_amd.synthetic import SceneConfig, make_fixed_map, make_sequence
-    cfg = SceneConfig(height=64, width=2048, seed=1234, step=0.2, yaw_rate=0.005)
-    scans, poses = make_sequence(cfg, 16)
-    even = list(range(0, 16, 2))
-    model = make_fixed_map(cfg, [scans[f] for f in even], poses[even], ref_frame=0, num_points=100_000)
-    rel = np.linalg.inv(poses[1]) @ poses[0]
-    model = (model.astype(np.float64) @ rel[:3, :3].T + rel[:3, 3]).astype(np.float32)
-    return {f: scans[f] for f in (3, 5, 7)}, poses, model
+    """bench.py's headline workload (shared: tests/iteration_audit.py)."""
+    from iteration_audit import bench_workload
+    scans, poses, model = bench_workload()
+    return {f: s.copy() for f, s in scans.items()}, poses.copy(), model.copy()
 
 
 def test_schedule_options_at_benchmark_size(torch_cuda):
