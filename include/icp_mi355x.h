@@ -444,6 +444,84 @@ void* icp_normal_equations_ptr(icp_ctx* ctx); /* device pointer, 32 doubles */
 /* use caller-owned device memory (e.g. a torch tensor RCCL can reduce in place) for the 32-double vector */
 int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
 
+/* ---- one call per odometry frame: ICPFrameToModel.do_process_next_frame (slam/odometry/icp_odometry.py:157-246) ------
+ * The frame loop of the reference behind two calls, for the kd-tree style map and either cost: what a caller otherwise
+ * composes from ten entry points above — the upload, the de-skew (Distortion.filter, slam/preprocessing.py:144-191), the
+ * grid sample (GridSample.filter :207-226) and its float32 cast (ToTensor :101-126), the projection and the choice of the
+ * targets (_read_input / sample_points, icp_odometry.py:319-358), the registration from the constant-velocity guess
+ * (ConstantVelocityInitialization, slam/initialization.py:103-119), the key-frame test and the map update (__update_map,
+ * icp_odometry.py:360-380) and the copy-out of `odometry_pc`.  The calls compose the entry points above in the order
+ * pylidar_slam_amd/odometry.py::MI355XICPFrameToModel issues them: per frame the same pose, parameters, iteration count,
+ * losses, steps, insertions and map, bit for bit.  No kernel of its own.
+ *   icp_odometry_init  ICPFrameToModel.init (:128-145): icp_map_init, frame counter 0, the motion since the last key frame
+ *                      and the last relative pose = identity.  Calling it again starts a new sequence on the same context
+ *                      (a frame launched and not ended is collected and dropped).
+ *   icp_frame_launch   enqueues one frame on the context's stream and returns without waiting.
+ *                      INPUT  xyz [n,3] float32.  ICP_MEM_HOST: one host copy into a pinned buffer of the context, one DMA
+ *                      on an upload stream of the context's own into one of two alternating device slots, the context's stream
+ *                      made to wait for it; a slot is overwritten by the frame after next — its last reader is the
+ *                      registration of its own frame, collected by then (icp_frame_end); `xyz` (and `timestamps`) are free
+ *                      when the call returns.  ICP_MEM_DEVICE: the rows are used in place and must stay untouched until
+ *                      icp_frame_end has returned.  timestamps [n] float64 live where xyz lives.
+ *                      DE-SKEW  with `timestamps` and an initial guess — init_pose, or the last relative pose under
+ *                      constant_velocity (identity for frames 0 and 1) — the frame is de-skewed by that guess (icp_distort)
+ *                      into float64 rows; without a guess (constant_velocity = 0 and init_pose = NULL) the frame passes through,
+ *                      as Distortion does without `init_rpose` (:157-162).
+ *                      GRID SAMPLE  voxel_size > 0: icp_grid_sample_padded of the float32 rows, or icp_grid_sample_padded_f64 of
+ *                      the de-skewed float64 rows followed by the (float)x cast — the chain icp_batch_preprocess documents, for
+ *                      one member.  Nothing is read back: the frame keeps its n rows, the samples first, NaN rows behind them.
+ *                      FRAME 0  projection and icp_map_update_vertex_map(identity, vertex map) (:176); no registration.
+ *                      LATER FRAMES  targets = 1: icp_project_rows, the targets are the pixels of the vertex map with
+ *                      ICP_TARGETS_SKIP_NULL (sample_points :301-308); targets = 0: the targets are the frame's rows and the
+ *                      vertex map — which the kd-tree branch reads nowhere behind frame 0 — is NOT built (the plugin builds it
+ *                      behind the registration and drops it).  Then icp_map_stage_cloud of the frame's rows (stage_max_rows), the
+ *                      copy of the staged rows towards the host on a stream of its own (copy_cloud), and icp_register_launch_from_last —
+ *                      under constant_velocity with init_pose = NULL, from frame 2 on, while the device still holds the last
+ *                      frame's pose — or icp_register_launch (init_pose; the last relative pose; identity).
+ *   icp_frame_end      icp_register_end: an error status (ICP_ERR_INVALID_JACOBIAN) is returned before the map is touched, as
+ *                      the reference raises at :286 — the frame counter, the last pose and the motion since the last key frame
+ *                      stay as they were.  Then __update_map (:360-380) on the host: new_delta = delta x pose in float32, its
+ *                      Euler parameters (Pose.from_pose_matrix, slam/common/pose.py:120-207), key frame when |t| >
+ *                      threshold_trans or |r| 180 / pi > threshold_rot; icp_map_update_staged (icp_map_update with the rows for a
+ *                      frame that was not staged) for a key frame (delta = identity),
+ *                      the pose-only icp_map_update otherwise (delta = new_delta) — enqueued, not waited for.
+ *                      odometry_pc_out (optional, `cap` rows, out_mem) receives the frame's valid rows in order (rows with a
+ *                      NaN dropped, :357: for a grid-sampled frame its samples), *rows_out their count (0 for a frame that was
+ *                      neither staged nor asked for its cloud: nobody counted its rows); more rows than `cap`:
+ *                      ICP_ERR_INVALID_ARGUMENT with the count in *rows_out and nothing written — the frame is completed all the
+ *                      same (result filled, map updated).  Frame 0 writes no rows, as the reference writes none (:171-181).
+ *                      loss_per_iter_out / dx_per_iter_out as for icp_register_end.
+ * ICP_ERR_INVALID_ARGUMENT with a message, the context usable as before: a context that holds a projective map, an exchange or
+ * profiling switched on, a context held by a batch, icp_frame_launch before icp_odometry_init or while a frame awaits its
+ * icp_frame_end, icp_frame_end with nothing launched.  Single-context entry points between the two calls follow the rules of
+ * icp_register_launch.  One frame at a time per context; a batched form (icp_batch_frame_*) does not exist. */
+typedef struct icp_frame_config {
+    double voxel_size;         /* > 0: GridSample (slam/preprocessing.py:207-226) in front of the frame; <= 0: the rows as given */
+    float threshold_trans;     /* key-frame test, metres (ICPFrameToModelConfig.threshold_trans, icp_odometry.py:29-64: 0.1) */
+    float threshold_rot;       /* key-frame test, degrees (threshold_rot: 0.3) */
+    int32_t constant_velocity; /* 1: initial guess = the last relative pose (slam/initialization.py:103-119); 0: identity */
+    int32_t targets;           /* 0: the frame's rows; 1: the pixels of its vertex map (sample_points, icp_odometry.py:301-308) */
+    int32_t copy_cloud;        /* 1: icp_frame_end will be asked for odometry_pc in host memory: its copy starts in
+                                  icp_frame_launch, beside the registration; 0: copied (if asked for) inside icp_frame_end */
+    int32_t stage_max_rows;    /* frames of more rows are NOT staged in front of their registration (a 131 072-row frame pays
+                                  more for the compaction on the way to its pose than the round trip behind it costs): a key
+                                  frame then goes in through icp_map_update with the rows.  Same map either way.  <= 0: always
+                                  staged; grid-sampled frames always are.  Default 32768 */
+} icp_frame_config;
+typedef struct icp_frame_result {
+    icp_register_result reg; /* frame 0: identity pose, zero parameters, 0 iterations */
+    int32_t frame_index;     /* 0 for the first frame behind icp_odometry_init */
+    int32_t key_frame;       /* 1: the frame went into the map (frame 0 always does) */
+    int64_t samples;         /* rows behind the grid sample (voxel_size <= 0: n) */
+    int64_t inserted;        /* rows appended to the map (0 for a pose-only update) */
+} icp_frame_result;
+void icp_default_frame_config(icp_frame_config* cfg);
+int icp_odometry_init(icp_ctx* ctx, const icp_frame_config* cfg);
+int icp_frame_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, const double* timestamps,
+                     const float init_pose[16]);
+int icp_frame_end(icp_ctx* ctx, icp_frame_result* result, float* odometry_pc_out, int64_t cap, int64_t* rows_out,
+                  int out_mem, double* loss_per_iter_out, float* dx_per_iter_out);
+
 /* ---- B sequences per launch: batched registration ------------------------------------------------------------------
  * The reference registers ONE sequence, one frame at a time (ICPFrameToModel.register_new_frame,
  * slam/odometry/icp_odometry.py:248-299; one `SLAM` object per process, slam/slam.py:84-163): a chain of dependent,

@@ -127,30 +127,7 @@ static constexpr size_t DBG_ITER_BYTES = 64 + 24 * 1024 * 4 * sizeof(long long);
 static constexpr size_t DBG_BYTES = DBG_ITER_BYTES + 8192 * 4 * sizeof(long long);  // dev statistics ("search_stats"): + the normal kernel's blocks
 
 // ---- helpers --------------------------------------------------------------------------------------------------------
-// Every entry point runs on the context's device and leaves the calling thread's current device as it found it (a
-// process may hold contexts on several GPUs, and torch shares the thread's current device with us).
-// ... and — `join` — orders itself behind a map update still running on the context's map stream ("overlap_map_update":
-// the re-expression, grid rebuild and normal estimation behind a registration run on a stream of their own, beside the next
-// frame's preprocessing on the caller's stream).  Entry points that touch neither the map nor its search structure nor the
-// registration state (projection, grid sample, de-skew, compaction of targets, the wait for a pose) do not join.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceGuard(const icp_ctx* ctx, bool join = true) : DeviceGuard(ctx ? ctx->cfg.device : -1) {
-        if (join && ctx && ctx->map_stream_busy) {
-            icp_ctx* c = const_cast<icp_ctx*>(ctx);
-            (void)hipStreamWaitEvent(c->stream, c->map_done_event, 0);
-            c->map_stream_busy = false;
-        }
-    }
-    explicit DeviceGuard(int device) {
-        if (device < 0) return;
-        if (hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
+// (DeviceGuard: icp_internal.h — frame.hip enters the library through it too)
 
 // Contexts of this process with a registration in flight, per device: the lead launches (and the resident tail) make the
 // workgroups of a launch wait for one another, which is only worth it — and only safe from a 50 ms bail-out — while no
@@ -187,10 +164,6 @@ struct RegisteringGuard {
     }
 };
 
-static int fail(icp_ctx* ctx, int code, const char* msg) {
-    if (ctx) ctx->error = msg;
-    return code;
-}
 
 // returns a device pointer for `n_bytes` of caller data (staging a host buffer through `stage`)
 static int import_buffer(icp_ctx* ctx, const void* src, size_t n_bytes, int mem, DeviceBuffer& stage,
@@ -238,7 +211,7 @@ static int ensure_state(icp_ctx* ctx) {
         const int newcap = cap > ctx->hist_cap ? cap : ctx->hist_cap;
         ICP_HIP(ctx, ctx->state.reserve(STATE_BLOCK + (size_t)newcap * (sizeof(double) + 6 * sizeof(float))));
         ctx->hist_cap = newcap;
-        ctx->have_device_pose = false;  // a fresh allocation holds no registration result
+        ctx->have_device_pose = false; ctx->device_pose_epoch += 1;  // a fresh allocation holds no registration result
         ctx->stats_pending = false;     // ... and no grid statistics
         ICP_HIP(ctx, hipMemsetAsync(ctx->state.ptr, 0, STATE_BLOCK, ctx->stream));
         ctx->loss_hist = (double*)(ctx->state.as<char>() + STATE_BLOCK);
@@ -354,6 +327,7 @@ void icp_destroy(icp_ctx* ctx) {
     DeviceGuard device_guard(ctx);
     registering_leave(ctx);
     (void)hipDeviceSynchronize();
+    frame_loop_release(ctx);
     DeviceBuffer* bufs[] = {&ctx->map_xyz[0], &ctx->map_xyz[1], &ctx->table,   &ctx->sorted_pts, &ctx->normals,
                             &ctx->nflag,      &ctx->slot_of,    &ctx->rank_of, &ctx->scan_tmp,   &ctx->worklist,
                             &ctx->targets,    &ctx->nn_pos,     &ctx->partials, &ctx->state,
@@ -1055,7 +1029,7 @@ int icp_nearest_neighbor_search(icp_ctx* ctx, const float* xyz, int64_t n, int m
     ctx->tgt_ptr = (const float*)in;
     ctx->tgt_n = n;
     ctx->tgt_mode = ICP_TARGETS_ALL;
-    ctx->have_device_pose = false;  // the search re-initialises the device state: it no longer holds a registration
+    ctx->have_device_pose = false; ctx->device_pose_epoch += 1;  // the search re-initialises the device state: it no longer holds a registration
     ICP_HIP(ctx, ctx->nn_pos.reserve((size_t)(n > 0 ? n : 1) * 4));
     if ((rc = prepare_targets_and_state(ctx, n, nullptr))) return rc;
     if ((rc = launch_search_raw(ctx))) return rc;
@@ -1299,7 +1273,7 @@ int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int ta
     ctx->tgt_n = n;
     ctx->tgt_mode = target_mode;
     if ((rc = prepare_targets_and_state(ctx, n, init_pose))) return rc;
-    ctx->have_device_pose = false;  // icp_map_update(rel_pose = NULL) follows a registration against the kd-tree style map only
+    ctx->have_device_pose = false; ctx->device_pose_epoch += 1;  // icp_map_update(rel_pose = NULL) follows a registration against the kd-tree style map only
     ctx->pm_have_pose = true;
     ctx->in_registration = true;
     const int iters = ctx->cfg.max_num_alignments;
@@ -1503,7 +1477,7 @@ static int register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, in
     ctx->tgt_mode = target_mode;
     ICP_HIP(ctx, ctx->nn_pos.reserve((size_t)(n > 0 ? n : 1) * 4));
     if ((rc = prepare_targets_and_state(ctx, n, init_pose, from_last, defer_pack))) return rc;
-    ctx->have_device_pose = true;
+    ctx->have_device_pose = true; ctx->device_pose_epoch += 1;
     // event pairs around the kernels of every `every`-th registration only: a pair costs ~2 us of stream time
     ctx->prof.sample_now = ctx->prof.every <= 1 || (ctx->prof.registrations % ctx->prof.every) == 0;
     ctx->prof.rotate_index = (int)((ctx->prof.registrations / (ctx->prof.every > 1 ? ctx->prof.every : 1)) %
@@ -2729,7 +2703,7 @@ int icp_batch_pmap_register_launch(icp_batch* b, const float* const* xyz, const 
         PackDesc* pack = reinterpret_cast<PackDesc*>(host) + i;
         const float* init = (init_poses && !from_last) ? init_poses + 16 * i : nullptr;
         if ((rc = prepare_targets_and_state(ctx, n[i], init, from_last != 0, pack))) return batch_fail(b, rc, ctx->error);
-        ctx->have_device_pose = false;  // (as icp_pmap_register)
+        ctx->have_device_pose = false; ctx->device_pose_epoch += 1;  // (as icp_pmap_register)
         ctx->in_registration = true;
         if ((rc = pmap_register_desc(ctx, host + pack_bytes + pmap_reg_desc_bytes() * i, &rows[i])))
             return batch_fail(b, rc, ctx->error);

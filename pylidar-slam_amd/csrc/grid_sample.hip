@@ -1010,6 +1010,14 @@ __global__ void k_rows_to_f32(const double* __restrict__ in, long long count, fl
     if (i < count) out[i] = (float)in[i];
 }
 
+int rows_to_f32_device(icp_ctx* ctx, const double* in_dev, int64_t count, float* out_dev) {
+    if (count <= 0) return ICP_OK;
+    hipLaunchKernelGGL(k_rows_to_f32, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, in_dev, (long long)count,
+                       out_dev);
+    ICP_HIP(ctx, hipGetLastError());
+    return ICP_OK;
+}
+
 static constexpr int64_t BUCKET_MAX_ROWS = 262144;  // (grid_sample_impl's bound of the bucket sort in the padded path)
 
 int preprocess_batch_device(icp_ctx* const* ctxs, int count, const icp_preprocess_frame* frames, double voxel) {

@@ -542,6 +542,8 @@ struct icp_ctx {
     // (icp_register_launch_from_last: its initial guess is read on the device) before the first one's result has been
     // collected, so the GPU never waits for the host between frames
     bool have_device_pose = false;   // RegState holds the pose of a finished / enqueued registration
+    long long device_pose_epoch = 0; // bumped wherever the RegState's pose is (re)initialised or given up: a caller that remembers the
+                                     // epoch of its own registration knows whether the device still holds THAT pose (frame.hip)
     struct ResultSlot {
         void* host = nullptr;
         size_t bytes = 0;
@@ -608,6 +610,8 @@ struct icp_ctx {
     std::vector<PmPose> pm_poses;              // pose of every kept map's frame in the current frame
     bool pm_have_pose = false;                 // the state holds the final pose of a registration against this map
     icp::Profile prof;
+    // ---- one call per odometry frame (frame.hip: icp_odometry_init / icp_frame_launch / icp_frame_end)
+    struct icp_frame_loop* frame = nullptr;    // created by icp_odometry_init, released by icp_destroy (frame_loop_release)
 };
 
 namespace icp {
@@ -620,6 +624,14 @@ namespace icp {
             return ICP_ERR_HIP;                                                                     \
         }                                                                                           \
     } while (0)
+
+inline int fail(icp_ctx* ctx, int code, const char* msg) {
+    if (ctx) ctx->error = msg;
+    return code;
+}
+
+// ---- frame.hip
+void frame_loop_release(icp_ctx* ctx);
 
 // ---- hash_grid.hip
 // defer != nullptr: everything but the launches — *defer receives their arguments (the caller launches them, e.g. for B maps
@@ -748,6 +760,8 @@ int voxel_hash_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, double voxe
                       long long* hashes_dev);
 int grid_sample_f64_device(icp_ctx* ctx, const double* xyz_dev, int64_t n, double voxel, long long* indices_dev,
                            double* points_dev, int* count_dev, int* count_host, bool padded = false);
+// (float)x of `count` doubles (the float32 copy ToTensor makes of de-skewed rows; NaN stays NaN)
+int rows_to_f32_device(icp_ctx* ctx, const double* in_dev, int64_t count, float* out_dev);
 int distort_device(icp_ctx* ctx, const float* xyz_dev, const double* ts_dev, int64_t n, const double* rel_pose16,
                    double* out_dev);
 // targets -> float4 rows (x, y, z, bits(row)) in ctx->tgt4
@@ -793,3 +807,28 @@ inline bool wants_eager_normals(const icp_ctx* ctx, int64_t n) {
 }
 
 }  // namespace icp
+
+// Every entry point runs on the context's device and leaves the calling thread's current device as it found it (a
+// process may hold contexts on several GPUs, and torch shares the thread's current device with us).
+// ... and — `join` — orders itself behind a map update still running on the context's map stream ("overlap_map_update":
+// the re-expression, grid rebuild and normal estimation behind a registration run on a stream of their own, beside the next
+// frame's preprocessing on the caller's stream).  Entry points that touch neither the map nor its search structure nor the
+// registration state (projection, grid sample, de-skew, compaction of targets, the wait for a pose) do not join.
+struct DeviceGuard {
+    int prev = -1;
+    bool switched = false;
+    explicit DeviceGuard(const icp_ctx* ctx, bool join = true) : DeviceGuard(ctx ? ctx->cfg.device : -1) {
+        if (join && ctx && ctx->map_stream_busy) {
+            icp_ctx* c = const_cast<icp_ctx*>(ctx);
+            (void)hipStreamWaitEvent(c->stream, c->map_done_event, 0);
+            c->map_stream_busy = false;
+        }
+    }
+    explicit DeviceGuard(int device) {
+        if (device < 0) return;
+        if (hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        if (switched) (void)hipSetDevice(prev);
+    }
+};

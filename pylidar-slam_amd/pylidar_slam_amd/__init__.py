@@ -12,7 +12,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # lazy: `engine` / `odometry` import torch
-    if name in ("IcpContext", "InvalidJacobianError", "RegisterResult"):
+    if name in ("IcpContext", "InvalidJacobianError", "RegisterResult", "FrameResult"):
         from . import engine
         return getattr(engine, name)
     if name in ("MI355XICPFrameToModel", "MI355XICPFrameToModelBatch", "MI355XICPConfig", "HashGridLocalMap", "PointToPlaneAlignment",

@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "load_library", "library_path",
+__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpFrameResult", "load_library", "library_path",
            "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -62,6 +62,19 @@ class IcpRegisterResult(C.Structure):
     _fields_ = [("pose", C.c_float * 16), ("params", C.c_float * 6), ("iterations", C.c_int32),
                 ("converged", C.c_int32), ("status", C.c_int32), ("num_targets", C.c_int32),
                 ("normals_computed", C.c_int64)]
+
+
+class IcpFrameConfig(C.Structure):
+    """icp_frame_config: the sequence settings of icp_odometry_init."""
+    _fields_ = [("voxel_size", C.c_double), ("threshold_trans", C.c_float), ("threshold_rot", C.c_float),
+                ("constant_velocity", C.c_int32), ("targets", C.c_int32), ("copy_cloud", C.c_int32),
+                ("stage_max_rows", C.c_int32)]
+
+
+class IcpFrameResult(C.Structure):
+    """icp_frame_result: what icp_frame_end returns for one frame."""
+    _fields_ = [("reg", IcpRegisterResult), ("frame_index", C.c_int32), ("key_frame", C.c_int32),
+                ("samples", C.c_int64), ("inserted", C.c_int64)]
 
 
 _P = C.c_void_p
@@ -127,6 +140,10 @@ EXPORTED_SYMBOLS = {
     "icp_iteration_accumulate": (_INT, [_P]),
     "icp_iteration_solve": (_INT, [_P]),
     "icp_register_end": (_INT, [_P, C.POINTER(IcpRegisterResult), _P, _P]),
+    "icp_default_frame_config": (None, [C.POINTER(IcpFrameConfig)]),
+    "icp_odometry_init": (_INT, [_P, C.POINTER(IcpFrameConfig)]),
+    "icp_frame_launch": (_INT, [_P, _P, _I64, _INT, _P, _P]),
+    "icp_frame_end": (_INT, [_P, C.POINTER(IcpFrameResult), _P, _I64, C.POINTER(_I64), _INT, _P, _P]),
     "icp_batch_create": (_INT, [_P, C.c_int32, C.POINTER(_P)]),
     "icp_batch_destroy": (None, [_P]),
     "icp_batch_last_error": (C.c_char_p, [_P]),

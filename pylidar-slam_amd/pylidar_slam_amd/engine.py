@@ -12,8 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (COSTS, IcpConfig, IcpLibraryError, IcpPreprocessFrame, IcpRegisterResult, MEM_DEVICE, MEM_HOST,
-                   SCHEMES, STATUS_MESSAGES, TARGETS_ALL, TARGETS_SKIP_NULL)
+from ._lib import (COSTS, IcpConfig, IcpFrameConfig, IcpFrameResult, IcpLibraryError, IcpPreprocessFrame,
+                   IcpRegisterResult, MEM_DEVICE, MEM_HOST, SCHEMES, STATUS_MESSAGES, TARGETS_ALL, TARGETS_SKIP_NULL)
 
 Array = Union[np.ndarray, torch.Tensor]
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> raw hipStream_t of torch's current stream
@@ -40,6 +40,25 @@ class RegisterResult:
     normals_computed: int
     losses: np.ndarray  # [iterations] f64
     dx: np.ndarray  # [iterations, 6] f32
+
+
+@dataclass
+class FrameResult:
+    """One frame of `IcpContext.frame_launch` / `frame_end` (icp_frame_result)."""
+    register: RegisterResult  # frame 0: the identity, 0 iterations
+    frame_index: int
+    key_frame: bool           # the frame went into the map (frame 0 always does)
+    samples: int              # rows behind the grid sample (no grid sample: the rows given)
+    inserted: int             # rows appended to the map (0: pose-only update)
+    points: Optional[np.ndarray]  # `odometry_pc`: the frame's valid rows [rows, 3] f32 (None: frame 0, or not asked for)
+
+    @property
+    def pose(self) -> np.ndarray:
+        return self.register.pose
+
+    @property
+    def params(self) -> np.ndarray:
+        return self.register.params
 
 
 def _ptr_mem(a: Optional[Array]) -> Tuple[Optional[int], int, object]:
@@ -712,6 +731,79 @@ class IcpContext:
         res = IcpRegisterResult()
         self._check_registration(self._lib.icp_register_end(self._h, C.byref(res), losses, dxs), res, losses, dxs)
         return self._result(res, losses, dxs)
+
+    # ---- one call per odometry frame ---------------------------------------------------------------------------------
+    def odometry_init(self, voxel_size: float = 0.0, threshold_trans: float = 0.1, threshold_rot: float = 0.3,
+                      constant_velocity: bool = True, targets: int = 0, copy_cloud: bool = True,
+                      stage_max_rows: int = 32768):
+        """`icp_odometry_init`: starts a sequence of `frame_launch` / `frame_end` on this context (empty map, frame 0).
+        voxel_size > 0: the grid sample in front of every frame; targets 0: the frame's rows, 1: the pixels of its vertex
+        map; constant_velocity: the initial guess of a frame is the last relative pose; copy_cloud: `frame_end` returns the
+        frame's valid rows (`odometry_pc`), copied beside the registration; stage_max_rows: larger raw frames are not
+        compacted in front of their registration (see icp_frame_config)."""
+        cfg = IcpFrameConfig()
+        self._lib.icp_default_frame_config(C.byref(cfg))
+        cfg.voxel_size, cfg.threshold_trans, cfg.threshold_rot = float(voxel_size), float(threshold_trans), float(threshold_rot)
+        cfg.constant_velocity, cfg.targets, cfg.copy_cloud = int(bool(constant_velocity)), int(targets), int(bool(copy_cloud))
+        cfg.stage_max_rows = int(stage_max_rows)
+        self._check(self._lib.icp_odometry_init(self._h, C.byref(cfg)))
+        self._frame_cfg = cfg
+        self._frame_keep = None
+        self._frame_rows = 0
+
+    def frame_launch(self, points: Array, timestamps: Optional[Array] = None, init_pose=None):
+        """`icp_frame_launch`: one frame — [N,3] float32 numpy rows (uploaded by the library through its pinned buffer) or a
+        cuda tensor (used in place: keep it untouched until `frame_end`) — enqueued without waiting.  timestamps [N]
+        float64 (where the points live): the frame is de-skewed by its initial guess.  init_pose: an explicit guess."""
+        self._bind(points)
+        if isinstance(points, torch.Tensor) and points.is_cuda:
+            pts = points if points.dtype == torch.float32 and points.is_contiguous() else \
+                points.to(torch.float32).contiguous()
+            ts = None
+            if timestamps is not None:
+                ts = torch.as_tensor(timestamps).to(pts.device, torch.float64).reshape(-1).contiguous()
+            mem, p, tp = MEM_DEVICE, pts.data_ptr(), ts.data_ptr() if ts is not None else None
+        else:
+            pts = points.numpy() if isinstance(points, torch.Tensor) else points
+            if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.flags.c_contiguous):
+                pts = np.ascontiguousarray(pts, dtype=np.float32)
+            ts = None
+            if timestamps is not None:
+                ts = np.ascontiguousarray(np.asarray(timestamps).reshape(-1), dtype=np.float64)
+            mem, p, tp = MEM_HOST, pts.ctypes.data, ts.ctypes.data if ts is not None else None
+        if pts.ndim != 2 or pts.shape[1] != 3 or (ts is not None and ts.shape[0] != pts.shape[0]):
+            raise AssertionError(f"expected [N,3] points (and [N] timestamps), got {tuple(pts.shape)}")
+        n = int(pts.shape[0])
+        self._check(self._lib.icp_frame_launch(self._h, p if n else None, n, mem, tp if n else None,
+                                               _pose16(init_pose) if init_pose is not None else None))
+        self._frame_keep = (pts, ts) if mem == MEM_DEVICE else None
+        self._frame_rows = n
+
+    def frame_end(self, with_points: Optional[bool] = None, cap: Optional[int] = None) -> FrameResult:
+        """`icp_frame_end`: waits for the frame's registration alone, applies the key-frame test and enqueues the map
+        update; returns the pose, the per-iteration histories, the decision and — with_points (default: as `copy_cloud`
+        of `odometry_init`) — the frame's valid rows.  An `Invalid Jacobian` raises before the map is touched."""
+        if with_points is None:
+            with_points = bool(getattr(self, "_frame_cfg", None) is not None and self._frame_cfg.copy_cloud)
+        rows_cap = int(getattr(self, "_frame_rows", 0)) if cap is None else int(cap)
+        hist = max(1, int(self.config.max_num_alignments))
+        losses = (C.c_double * hist)()
+        dxs = (C.c_float * (6 * hist))()
+        res = IcpFrameResult()
+        count = C.c_int64(0)
+        out = np.empty((max(rows_cap, 1), 3), np.float32) if with_points else None
+        rc = self._lib.icp_frame_end(self._h, C.byref(res), out.ctypes.data if out is not None else None, rows_cap,
+                                     C.byref(count) if with_points else None, MEM_HOST, losses, dxs)
+        self._frame_keep = None
+        try:
+            self._check_registration(rc, res.reg, losses, dxs)
+        except AssertionError as e:  # (`cap` below the frame's rows: the frame is completed all the same)
+            e.rows, e.result, e.register = int(count.value), res, self._result(res.reg, losses, dxs)
+            raise
+        first = int(res.frame_index) == 0
+        points = out[:int(count.value)] if (out is not None and not first) else None
+        return FrameResult(self._result(res.reg, losses, dxs), int(res.frame_index), bool(res.key_frame), int(res.samples),
+                           int(res.inserted), points)
 
     def raise_for_status(self, rc: int):
         """Maps a status code of the C ABI to the exception the reference raises (public form of the internal check)."""

@@ -927,6 +927,10 @@ class MI355XICPConfig:
     # masks the null ones inside its kernels (False: the valid queries stay spread over all 256 workgroups of a launch instead
     # of filling 12 — measured in round 5 on the published configuration: 0.52-0.55 vs 0.60 ms per frame)
     compact_sparse_vertex_map: bool = False
+    # True: a frame is ONE pair of library calls (icp_frame_launch + icp_frame_end, include/icp_mi355x.h) instead of the ten
+    # calls of do_process_next_frame below — the same poses, iterations, insertions and map, bit for bit.  numpy [N, 3] and
+    # cuda [N, 3] frames against the kd-tree style map; anything else is refused with the reason, not routed elsewhere
+    one_call_frame: bool = False
 
 
 def _get(obj, key, default=None):
@@ -1000,6 +1004,14 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         self._dev_in, self._dev_slot = [None, None], 0
         self._register_threshold_trans = config.threshold_trans
         self._register_threshold_rot = config.threshold_rot
+        self._one_call = bool(_get(config, "one_call_frame", False))
+        self._one_call_targets = None
+        if self._one_call:
+            assert_debug(not self._projective, "one_call_frame: the frame calls of the library run the kd-tree style local "
+                                               "map, not the projective one")
+            assert_debug(not bool(_get(config, "compact_sparse_vertex_map", False)),
+                         "one_call_frame: compact_sparse_vertex_map is a schedule of the per-call path only")
+            assert_debug(hasattr(self.ctx, "frame_launch"), "one_call_frame needs the library's frame calls")
 
     def init(self):  # :128-145
         super().init()
@@ -1123,6 +1135,8 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         registration alone (`icp_register_end`); the map update is enqueued from the pose without waiting for it, so it
         overlaps the caller's preparation of the next frame."""
         self.ctx.use_torch_stream()
+        if self._one_call:
+            return self._one_call_next_frame(data_dict)
         self._read_input(data_dict)
         if self._iter == 0:
             eye = np.eye(4, dtype=np.float32)
@@ -1163,6 +1177,65 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         self.absolute_poses.append(self.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64),
                                                                                  np.float64)))  # :200-202
         data_dict[self.pointcloud_key()] = tgt_np_pc  # :243
+        data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+        self._iter += 1
+
+    def _one_call_next_frame(self, data_dict: dict):
+        """`one_call_frame`: the frame through icp_frame_launch + icp_frame_end.  The library uploads a numpy frame, projects,
+        stages, registers from `init_rpose`, applies the key-frame test of `__update_map` and updates the map; what stays
+        here is the pose chain and the outputs written to the dict.  The initial guess stays the dict's `init_rpose` (the
+        initialisation is a module of its own in the reference, slam/slam.py:126-140), handed over explicitly with every frame:
+        the library's own constant-velocity mode (the guess read on the device) is for callers without such a module."""
+        key = self.config.data_key
+        assert_debug(key in data_dict, f"Could not find the key `{key}` in the input dictionary.\n"
+                                       f"With keys : {data_dict.keys()}). Set the parameter "
+                                       f"`slam.odometry.data_key` to the desired key")
+        data = data_dict[key]
+        is_numpy = isinstance(data, np.ndarray)
+        assert_debug(is_numpy or (isinstance(data, torch.Tensor) and data.is_cuda and data.ndim == 2),
+                     "one_call_frame covers numpy [N, 3] and cuda [N, 3] frames: a vertex-map tensor (or a cpu tensor) goes "
+                     "through the per-call path (one_call_frame=False), got "
+                     f"{type(data).__name__} {tuple(getattr(data, 'shape', ()))}")
+        assert_debug(data.ndim == 2 and data.shape[1] == 3, f"expected [N, 3], got {tuple(data.shape)}")
+        if is_numpy:
+            self._sample_pointcloud = True  # sticky (:330)
+        targets = 0 if self._sample_pointcloud else 1  # sample_points :301-308
+        want_rows = "distorted" not in data_dict  # (:210-213)
+        # (`odometry_pc` of a numpy frame is made from the host rows the caller handed over, as on the per-call path: nothing
+        # to copy back; a tensor frame's valid rows come back from the library, copied beside the registration)
+        from_device = want_rows and not is_numpy
+        if self._iter == 0:
+            self.ctx.odometry_init(voxel_size=0.0, threshold_trans=self._register_threshold_trans,
+                                   threshold_rot=self._register_threshold_rot, constant_velocity=False, targets=targets,
+                                   copy_cloud=from_device,
+                                   # (a frame that comes padded from the device-resident grid sample is staged whatever its
+                                   # row count, as do_process_next_frame does: `sample_count` says so at frame 0)
+                                   stage_max_rows=0 if data_dict.get("sample_count", None) is not None else
+                                   int(_get(self.config, "stage_insert_max_rows", 32768)))
+            self._one_call_targets = targets
+        assert_debug(targets == self._one_call_targets, "one_call_frame: numpy and tensor frames were mixed within one "
+                                                        "sequence (the targets of a sequence are its rows or its pixels)")
+        self._host_rows = None
+        if is_numpy:
+            self._host_rows = data if data.dtype == np.float32 and data.flags.c_contiguous else \
+                np.ascontiguousarray(data, dtype=np.float32)
+        self.ctx.frame_launch(self._host_rows if is_numpy else data, None,
+                              self._initial_pose(data_dict) if self._iter > 0 else None)
+        tgt_np_pc = self._rows_to_host(None) if (want_rows and is_numpy and self._iter > 0) else None  # GPU busy meanwhile
+        res = self.ctx.frame_end(with_points=from_device and self._iter > 0)  # raises before the map is touched (:286)
+        if self._iter == 0:
+            self.relative_poses.append(np.eye(4, dtype=np.float32)[None])
+            self.absolute_poses.append(np.eye(4, dtype=np.float64))
+            self._iter += 1
+            return
+        self.last_result = res.register
+        pose, params = res.register.pose, res.register.params
+        self.relative_poses.append(pose[None].copy())
+        self.absolute_poses.append(self.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64),
+                                                                                 np.float64)))  # :200-202
+        if want_rows and not is_numpy:
+            tgt_np_pc = res.points.copy()
+        data_dict[self.pointcloud_key()] = tgt_np_pc if want_rows else data_dict["distorted"]  # :243
         data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
         self._iter += 1
 
