@@ -428,7 +428,7 @@ class KdTreeLocalMapOracle:
             self.local_map = numpy_pc
             self.num_elements.append(num)
         else:
-            inv = np.linalg.inv(rel_pose)  # :346 (float32 LAPACK)
+            inv = np.linalg.inv(rel_pose)  # :346 (float32 in: numpy computes in double and rounds the inverse back to float32)
             moved = (np.einsum("ij,nj->ni", inv[:3, :3], self.local_map) + inv[:3, 3].reshape(1, 3)).astype(F32)
             if numpy_pc is not None:
                 self.local_map = np.concatenate([moved, numpy_pc], axis=0)

@@ -29,6 +29,7 @@ ICP_OK, ICP_ERR_INVALID_JACOBIAN = 0, -3
 STEP_ATOL = 2.0e-7  # projective_cases.assert_step: dx atol 2e-7 / rtol 2e-5, loss 1e-5
 MISMATCH_CAP = 1.0e-3  # share of valid rows whose neighbour may differ from the kd-tree's (the `> 0.999` of the C2 tests)
 TIE_RTOL = 2.0e-6  # ... each of them a squared-distance tie within this (the `rtol=2e-6` of the C2 tests)
+TIE_ABS = 1.0e-12  # ... or closer than this in absolute squared distance (m^2: coincident points)
 NORMAL_DOT, NORMAL_UNIT = 1.0e-5, 1.0e-5
 POSE_ATOL = 1.0e-6  # test_register_masks_nan_and_null_rows
 COSTS = ("point_to_plane", "point_to_point")
@@ -227,7 +228,7 @@ def check_neighbours(rec, targets, map_points, skip_null, tree=None, low=None):
     fig["share"] = float(differ.mean())
     if differ.any():
         rel = np.abs(used[differ] - bd[differ] ** 2) / np.maximum(bd[differ] ** 2, 1e-300)
-        rel = np.where(np.abs(used[differ] - bd[differ] ** 2) <= 1e-12, 0.0, rel)
+        rel = np.where(np.abs(used[differ] - bd[differ] ** 2) <= TIE_ABS, 0.0, rel)
         fig["worst_tie"] = float(rel.max())
         if (rel > TIE_RTOL).any():
             fails.append(("neighbours", f"iteration {rec.k}: {(rel > TIE_RTOL).sum()} of {differ.sum()} mismatches are no "

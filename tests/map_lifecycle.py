@@ -1,0 +1,492 @@
+"""The kd-tree local map held to a bit model after every update (tests/test_map_lifecycle.py on the CPU,
+tests/test_gpu_map_lifecycle.py on the device).  TEST INFRASTRUCTURE: numpy + scipy + tests/iteration_audit.py, importable
+without a GPU, never imported by the package.
+
+`KdTreeLocalMap.update` (reference slam/odometry/local_map.py:302-362) is arithmetic one can state exactly:
+
+  invert4      a float64 Gauss-Jordan with partial pivoting, every row update `a[r] - f * a[c]` as two roundings, the result
+               rounded to float32 (csrc/map_move_device.h) — np.linalg.inv of a float32 matrix computes in double and rounds
+               back, which is why the reference and the library agree;
+  move         ((T0 x + T1 y) + T2 z) + T3, every float32 operation rounded on its own;
+  bookkeeping  NaN rows dropped (and (0,0,0) rows under skip_null), a first cloud taken as it is with its pose ignored, the
+               count of EVERY cloud recorded (zero rows included), the first count popped — and that many rows dropped
+               from the FRONT — once more than `local_map_size` counts are held; `map_set` records no count.
+
+`MapModel` is that in numpy, with a float64 shadow beside it: the same bookkeeping with np.linalg.inv in float64 and
+float64 points, and per point a bound on the Euclidean distance between the two that grows with every move the point lived
+through by 5 * 2^-24 * || |R^-1| |p| + |t^-1| ||_2 (three roundings of the chain, one of the first product, one of the
+float32 inverse; the rotation carries the error of the earlier moves over unchanged in norm).  The bit check has power
+the bound has not: the same move with its additions contracted to fma stays inside the bound and differs in about a
+quarter of the coordinates.
+
+No tolerance is introduced here except that derived bound: the search and the normals are held at the bars of
+tests/iteration_audit.py (TIE_RTOL, MISMATCH_CAP, check_normals).
+"""
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import Optional
+
+import numpy as np
+
+import iteration_audit as A
+
+F32, F64 = np.float32, np.float64
+U32 = F32(2.0 ** -24)
+VMAP_THRESHOLD = F32(0.01)
+SCHEME, SIGMA, K_REG = "geman_mcclure", 0.3, 4
+H, W = 16, 256
+MUTANTS = ("evict_back", "pop_new_count", "zero_cloud_uncounted", "set_counted", "first_cloud_moved", "rel_not_inverted",
+           "rotation_transposed", "fma_move", "nan_row_kept", "null_row_kept", "vmap_threshold_ge")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the arithmetic
+# ----------------------------------------------------------------------------------------------------------------------
+def invert4(rel32):
+    """invert4 of csrc/map_move_device.h on the float32 4x4 `_pose16` hands over; None on a zero pivot."""
+    a = np.zeros((4, 8), F64)
+    a[:, :4] = np.asarray(rel32, F32).reshape(4, 4).astype(F64)
+    a[:, 4:] = np.eye(4)
+    for c in range(4):
+        piv = c
+        for r in range(c + 1, 4):
+            if abs(a[r, c]) > abs(a[piv, c]):
+                piv = r
+        if a[piv, c] == 0.0:
+            return None
+        if piv != c:
+            a[[c, piv]] = a[[piv, c]]
+        a[c] = a[c] * (1.0 / a[c, c])
+        for r in range(4):
+            if r != c:
+                f = a[r, c]
+                a[r] = a[r] - f * a[c]  # (numpy: a product and a difference, each rounded)
+    return a[:, 4:].astype(F32)
+
+
+def move(T, pts):
+    """move_point: ((T0 x + T1 y) + T2 z) + T3 in float32, column by column."""
+    T = np.asarray(T, F32)
+    p = np.asarray(pts, F32).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    out = np.empty_like(p)
+    for i in range(3):
+        out[:, i] = ((T[i, 0] * x + T[i, 1] * y) + T[i, 2] * z) + T[i, 3]
+    return out
+
+
+def move_fma(T, pts):
+    """The same chain with its additions contracted: fma(z, T2, fma(y, T1, x T0)) + T3 (projective_cases.transform_fma)."""
+    return A.transform_fma(pts, np.asarray(T, F32).reshape(4, 4))
+
+
+def vertex_map_rows(vmap, ge=False):
+    """[3,H,W] -> the pixels in row-major order with sqrt(fl(fl(x^2 + y^2) + z^2)) > float32(0.01) (NaN compares false)."""
+    v = np.asarray(vmap, F32).reshape(3, -1)
+    x, y, z = v[0], v[1], v[2]
+    with np.errstate(invalid="ignore"):
+        nrm = np.sqrt(((x * x + y * y) + z * z).astype(F32))
+        keep = nrm >= VMAP_THRESHOLD if ge else nrm > VMAP_THRESHOLD
+    return np.ascontiguousarray(v.T[keep])
+
+
+class MapModel:
+    """The reference's `_local_map` / `_local_map_num_elements` to the bit, the float64 shadow and its bound beside them.
+    `mutant`: one of MUTANTS — a deliberately wrong copy (tests/test_map_lifecycle.py)."""
+
+    def __init__(self, local_map_size, mutant=None):
+        assert mutant is None or mutant in MUTANTS, mutant
+        self.size, self.mutant = int(local_map_size), mutant
+        self.init()
+
+    def init(self):
+        self.points: Optional[np.ndarray] = None  # None: no map yet (the next cloud is a first cloud)
+        self.counts = []
+        self.shadow = np.zeros((0, 3), F64)
+        self.bound = np.zeros(0, F64)
+        self.inserted = 0
+        self.evicted = 0
+
+    def set(self, points):
+        self.init()
+        self.points = np.ascontiguousarray(np.asarray(points, F32).reshape(-1, 3)).copy()
+        self.shadow, self.bound = self.points.astype(F64), np.zeros(len(self.points), F64)
+        if self.mutant == "set_counted":
+            self.counts.append(len(self.points))
+
+    @property
+    def map(self):
+        return self.points if self.points is not None else np.zeros((0, 3), F32)
+
+    def __len__(self):
+        return len(self.map)
+
+    def filter(self, cloud, skip_null):
+        c = np.asarray(cloud, F32).reshape(-1, 3)
+        ok = ~np.isnan(c).any(axis=1)
+        if self.mutant == "nan_row_kept" and (~ok).any():
+            ok[np.nonzero(~ok)[0][0]] = True
+        if skip_null:
+            null = (c == 0).all(axis=1)
+            if self.mutant == "null_row_kept" and null.any():
+                null[np.nonzero(null)[0][0]] = False
+            ok &= ~null
+        return np.ascontiguousarray(c[ok])
+
+    def update(self, rel, cloud=None, skip_null=False):
+        """Returns the number of inserted rows; None (nothing changed) for a singular `rel`."""
+        rel32 = np.asarray(rel, F32).reshape(4, 4)
+        new = None if cloud is None else self.filter(cloud, skip_null)
+        n = 0 if new is None else len(new)
+        self.evicted = 0
+        if self.points is None and not self.counts:
+            assert new is not None, "a pose-only update of a map that was never given a cloud is not modelled"
+            self.points = new.copy()
+            self.shadow, self.bound = new.astype(F64), np.zeros(n, F64)
+            if self.mutant == "first_cloud_moved":
+                self.points = move(invert4(rel32), self.points)
+            self.counts.append(n)
+            self.inserted = n
+            return n
+        inv = invert4(rel32)
+        if inv is None:
+            return None
+        inv64 = np.linalg.inv(rel32.astype(F64))
+        if self.mutant == "rel_not_inverted":
+            inv = rel32
+        elif self.mutant == "rotation_transposed":
+            inv = inv.copy()
+            inv[:3, :3] = inv[:3, :3].T.copy()
+        moved = (move_fma if self.mutant == "fma_move" else move)(inv, self.points)
+        r64, t64 = inv64[:3, :3], inv64[:3, 3]
+        self.bound = self.bound + 5.0 * float(U32) * np.linalg.norm(np.abs(self.shadow) @ np.abs(r64).T + np.abs(t64), axis=1)
+        self.shadow = self.shadow @ r64.T + t64
+        if new is not None:
+            moved = np.concatenate([moved, new])
+            self.shadow = np.concatenate([self.shadow, new.astype(F64)])
+            self.bound = np.concatenate([self.bound, np.zeros(n, F64)])
+            if not (self.mutant == "zero_cloud_uncounted" and n == 0):
+                self.counts.append(n)
+        if len(self.counts) > self.size:
+            first = self.counts.pop(-1 if self.mutant == "pop_new_count" else 0)
+            keep = slice(0, max(len(moved) - first, 0)) if self.mutant == "evict_back" else slice(first, None)
+            self.evicted = min(first, len(moved))
+            moved, self.shadow, self.bound = moved[keep], self.shadow[keep], self.bound[keep]
+        self.points = np.ascontiguousarray(moved)
+        self.inserted = n
+        return n
+
+    def update_vertex_map(self, rel, vmap):
+        return self.update(rel, vertex_map_rows(vmap, ge=self.mutant == "vmap_threshold_ge"))
+
+    def check_against_float64(self):
+        """|model - shadow|_2 <= bound for every point; returns the worst ratio (0 for an empty map)."""
+        if not len(self):
+            return 0.0
+        err = np.linalg.norm(self.points.astype(F64) - self.shadow, axis=1)
+        fresh = self.bound == 0
+        assert not err[fresh].any(), "a point that was never moved differs from its float64 shadow"
+        ratio = float((err[~fresh] / self.bound[~fresh]).max()) if (~fresh).any() else 0.0
+        assert ratio <= 1.0, f"the model left its float64 shadow: {ratio:.3f} x the derived bound"
+        return ratio
+
+
+def first_difference(got, want):
+    """None where two float32 [m,3] arrays have the same bits, else a description of the first differing row."""
+    got, want = np.ascontiguousarray(got, F32), np.ascontiguousarray(want, F32)
+    if got.shape != want.shape:
+        return f"shape {got.shape} vs {want.shape}"
+    diff = (got.view(np.uint32) != want.view(np.uint32)).any(axis=1)
+    if not diff.any():
+        return None
+    r = int(np.nonzero(diff)[0][0])
+    return (f"{int(diff.sum())} of {len(got)} rows differ, the first at row {r}: {got[r]!r} ({got[r].view(np.uint32)}) vs "
+            f"{want[r]!r} ({want[r].view(np.uint32)})")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# scripts
+# ----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class Op:
+    kind: str  # "init" | "set" | "update"
+    rel: Optional[np.ndarray] = None  # [4,4] f32
+    cloud: Optional[np.ndarray] = None  # [n,3] f32 | None: pose-only ("set": the points)
+    skip_null: bool = False
+    frame: Optional[int] = None  # the scan whose frame the update leads to (None: a pose that is no frame of the sequence)
+    register: Optional[int] = None  # the scan to register behind this operation (check_registration), with ...
+    init: Optional[np.ndarray] = None  # ... this initial pose
+    note: str = ""
+
+
+@dataclass
+class Script:
+    name: str
+    local_map_size: int
+    ops: list
+    scans: list
+
+
+_CACHE = {}
+JITTER = ([0.01, -0.02, 0.005, 0.001, -0.002, 0.003], [-0.015, 0.01, -0.004, -0.002, 0.001, -0.0015],
+          [0.3, -0.1, 0.02, 0.004, -0.003, 0.02])
+
+
+def _sequence():
+    if "seq" not in _CACHE:
+        from pylidar_slam_amd.synthetic import SceneConfig, make_fixed_map, make_sequence
+        cfg = SceneConfig(height=H, width=W)
+        scans, poses = make_sequence(cfg, 12)
+        rel = [np.eye(4, dtype=F32)] + [(np.linalg.inv(poses[f - 1]) @ poses[f]).astype(F32) for f in range(1, 12)]
+        fixed = make_fixed_map(cfg, scans[:3], poses[:3], ref_frame=2, num_points=3000)
+        _CACHE["seq"] = (scans, rel, np.ascontiguousarray(fixed, F32))
+    return _CACHE["seq"]
+
+
+def _jitter(i):
+    return A.O.build_pose_matrix(np.array(JITTER[i], F32)).astype(F32)
+
+
+def _mixed_cloud(scan, n, seed):
+    """n rows of the scan of which some are NaN (one coordinate or all three) and some exactly (0, 0, 0)."""
+    c = A.subset(scan, n).copy()
+    rng = np.random.default_rng(seed)
+    rows = rng.choice(n, 40, replace=False)
+    c[rows[:12], 1] = np.nan
+    c[rows[12:24]] = np.nan
+    c[rows[24:]] = 0.0
+    c[rows[30], 2] = F32(-0.0)  # (-0.0 == 0: a null row too)
+    return c
+
+
+def script(name):
+    if name in _CACHE:
+        return _CACHE[name]
+    scans, rel, fixed = _sequence()
+    sub, U = A.subset, lambda f, cloud=None, **kw: Op("update", rel[f], cloud, frame=f, **kw)  # noqa: E731
+    if name == "window":
+        mixed8, mixed9 = _mixed_cloud(scans[8], 600, 8), _mixed_cloud(scans[9], 600, 9)
+        ops = [
+            Op("update", _jitter(2), sub(scans[0], 1639), note="first cloud, its pose ignored"),
+            U(1, sub(scans[1], 1), note="one row"),
+            U(2, note="pose only"),
+            U(3, sub(scans[3], 255)),
+            U(4, sub(scans[4], 256), register=5, init=rel[5], note="first eviction: a full cloud"),
+            U(5, np.zeros((0, 3), F32), note="0 rows, evicts the 1-row cloud"),
+            U(6, note="pose only"),
+            Op("update", _jitter(0), None, register=6, init=invert4(_jitter(0)), note="pose only, the second in a row"),
+            U(7, np.full((300, 3), np.nan, F32), note="all NaN: inserted 0, counted"),
+            U(8, mixed8, skip_null=False, note="NaN and null rows, the null rows kept"),
+            U(9, mixed9, skip_null=True, register=10, init=rel[10], note="NaN and null rows skipped; evicts a 0-row cloud"),
+            U(10, sub(scans[10], 257), note="evicts the other 0-row cloud"),
+            Op("update", _jitter(1), None, note="pose only"),
+            U(11, sub(scans[11], 1639), note="evicts the cloud with the null rows"),
+        ]
+        out = Script(name, 3, ops, scans)
+    elif name == "window_one":
+        ops = [
+            Op("update", _jitter(2), sub(scans[0], 600), note="first cloud"),
+            U(1, sub(scans[1], 513), register=2, init=rel[2], note="evicts everything before it"),
+            U(2, note="pose only"),
+            U(3, np.zeros((0, 3), F32), note="0 rows: an empty map"),
+            U(4, note="pose only, of an empty map"),
+            U(5, sub(scans[5], 400), note="the update behind the empty map"),
+            U(6, note="pose only"),
+            U(7, sub(scans[7], 257)),
+        ]
+        out = Script(name, 1, ops, scans)
+    elif name == "set_then_update":
+        ops = [
+            Op("set", cloud=fixed, note="map_set: no count"),
+            U(3, sub(scans[3], 400)),
+            U(4, sub(scans[4], 256)),
+            U(5, sub(scans[5], 500), register=6, init=rel[6], note="pops the count of the first INSERTED cloud: 400 rows of "
+                                                                   "the map_set points go"),
+            Op("init", note="map_init"),
+            Op("update", _jitter(2), sub(scans[6], 600), note="a new first cloud"),
+            U(7, sub(scans[7], 300)),
+        ]
+        out = Script(name, 2, ops, scans)
+    elif name == "drift":
+        d = _jitter(2)
+        back = invert4(d)
+        ops = [Op("update", np.eye(4, dtype=F32), sub(scans[0], 1639)), U(1, sub(scans[1], 800)), U(2, sub(scans[2], 1200))]
+        ops += [Op("update", d if i % 2 == 0 else back, None, note=f"drift {i}") for i in range(40)]
+        ops[-1].register, ops[-1].init = 3, rel[3]
+        out = Script(name, 3, ops, scans)
+    else:
+        raise KeyError(name)
+    _CACHE[name] = out
+    return out
+
+
+SCRIPTS = ("window", "window_one", "set_then_update", "drift")
+PLANE_SEEDS = (1, 2)  # the seeds of the two searches test_refusals_leave_the_map_alone makes on the plane map
+
+
+def plane_inputs():
+    """(rel, two clouds) of the refusal test's Invalid-Jacobian case: the jittered grid on z = 0 of A.plane_case in two
+    halves, moved IN the plane (a yaw and an x / y shift: z stays exactly 0)."""
+    pmap, _ = A.plane_case()
+    rel = A.O.build_pose_matrix(np.array([0.3, -0.1, 0.0, 0.0, 0.0, 0.02], F32)).astype(F32)
+    return rel, (pmap[:2048], pmap[2048:])
+RECORDED = ("window", "window_one", "set_then_update")  # run through the reference's KdTreeLocalMap: tests/golden/map_lifecycle.npz
+# the two steps of `window` whose search the reference recorded: the one before and the one directly behind the first
+# eviction (1639 rows); the probes of the first are displaced from the rows that survive it
+RECORDED_SEARCH = ((3, 1639), (4, 0))  # (operation, first_row of displaced_probes)
+
+
+def apply(model, op):
+    """One operation on the model; returns `inserted` (None for init / set)."""
+    if op.kind == "init":
+        model.init()
+        return None
+    if op.kind == "set":
+        model.set(op.cloud)
+        return None
+    return model.update(op.rel, op.cloud, op.skip_null)
+
+
+def states(name, mutant=None):
+    """The model behind every operation of a script: a list of (points copy, counts copy, inserted)."""
+    s = script(name)
+    m = MapModel(s.local_map_size, mutant)
+    out = []
+    for op in s.ops:
+        ins = apply(m, op)
+        out.append((m.map.copy(), list(m.counts), ins))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# search
+# ----------------------------------------------------------------------------------------------------------------------
+N_DISPLACED, N_FAR = 512, 64
+
+
+def displaced_probes(map_points, seed, first_row=0):
+    """512 map points (of those from `first_row` on) displaced by N(0, 0.05 m)."""
+    m = np.asarray(map_points, F32)
+    rng = np.random.default_rng(seed)
+    rows = rng.integers(first_row, len(m), N_DISPLACED)
+    return np.ascontiguousarray((m[rows].astype(F64) + rng.normal(0.0, 0.05, (N_DISPLACED, 3))).astype(F32))
+
+
+def search_probes(map_points, seed):
+    """Every map point itself, then 512 map points displaced by N(0, 0.05 m), then 64 points 50 - 400 m away."""
+    m = np.asarray(map_points, F32)
+    rng = np.random.default_rng(seed + 1000)
+    d = rng.normal(size=(N_FAR, 3))
+    far = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(50.0, 400.0, (N_FAR, 1))
+    return np.ascontiguousarray(np.concatenate([m, displaced_probes(m, seed), far.astype(F32)]))
+
+
+def tie_census(map_points, probes, tree=None):
+    """Share of the probes whose two nearest float64 distances (to DIFFERENT coordinates) tie within A.TIE_RTOL."""
+    m = np.asarray(map_points, F32).astype(F64)
+    if len(m) < 2:
+        return 0.0
+    low = A.lowest_index_of_equal_points(map_points)
+    tree = tree or A.cKDTree(m)
+    k = min(len(m), 8)
+    d, ix = tree.query(np.asarray(probes, F32).astype(F64), k=k, workers=-1)
+    other = low[ix] != low[ix[:, :1]]  # the nearest point at other coordinates than the nearest
+    has = other.any(axis=1)
+    second = d[np.arange(len(d)), other.argmax(axis=1)] ** 2
+    first = d[:, 0] ** 2
+    tie = has & (np.abs(second - first) <= A.TIE_RTOL * np.maximum(first, 1e-300))
+    return float(tie.mean())
+
+
+def verify_search(tag, map_points, probes, nb, nm, ix, nref, n_self=0):
+    """The answer of a nearest-neighbour search of `probes` (the first n_self of them the map points themselves, in order)
+    against the map the MODEL says is there.  Returns the figures."""
+    m = np.asarray(map_points, F32)
+    ix = np.asarray(ix).astype(np.int64)
+    p = np.asarray(probes, F32).astype(F64)
+    assert ix.shape == (len(p),), f"{tag}: {ix.shape} indices for {len(p)} probes"
+    assert (ix >= 0).all() and (ix < len(m)).all(), f"{tag}: a neighbour index outside the map of {len(m)} points"
+    if nb is not None:
+        why = first_difference(nb, m[ix])
+        assert why is None, f"{tag}: neighbor_points are not the model's points at the returned indices: {why}"
+    m64 = m.astype(F64)
+    bd, bi = nref.tree.query(p, workers=-1)
+    used = ((p - m64[ix]) ** 2).sum(axis=1)
+    best = ((p - m64[bi]) ** 2).sum(axis=1)
+    low = A.lowest_index_of_equal_points(m)
+    differ = low[ix] != low[bi]
+    fig = dict(probes=len(p), mismatches=int(differ.sum()), share=float(differ.mean()) if len(p) else 0.0, worst_tie=0.0)
+    if differ.any():
+        gap = np.abs(used[differ] - best[differ])
+        rel = np.where(gap <= A.TIE_ABS, 0.0, gap / np.maximum(best[differ], 1e-300))
+        fig["worst_tie"] = float(rel.max())
+        r = int(np.nonzero(differ)[0][rel.argmax()])
+        assert (rel <= A.TIE_RTOL).all(), \
+            (f"{tag}: {(rel > A.TIE_RTOL).sum()} of {len(p)} neighbours are not the nearest map point of the model (worst: probe "
+             f"{r} -> index {ix[r]} at d2 {used[r]:.6e}, the model's nearest {bi[r]} at {best[r]:.6e})")
+    assert fig["share"] <= A.MISMATCH_CAP, f"{tag}: {fig['mismatches']} of {len(p)} neighbours differ from the model's"
+    if n_self:
+        own = used[:n_self]
+        assert not own.any(), f"{tag}: {(own != 0).sum()} map points do not find themselves (worst d2 {own.max():.3e})"
+        bad = ix[:n_self] != low[:n_self]
+        assert not bad.any(), f"{tag}: {bad.sum()} map points find an equal point that is not the lowest index"
+    if nm is not None:
+        normals = np.full((len(m), 3), np.nan, F32)
+        normals[ix] = np.asarray(nm, F32)
+        again = first_difference(normals[ix], nm)
+        assert again is None, f"{tag}: two probes with the same neighbour were given different normals: {again}"
+        fails, nfig = A.check_normals(SimpleNamespace(k=tag, ix=ix), normals, nref)
+        assert not fails, f"{tag}: " + "; ".join(w for _, w in fails)
+        fig.update(used=nfig["used"], clear=nfig["clear"], min_dot=nfig["min_dot"])
+    return fig
+
+
+def check_state(ctx, model, tag, inserted=None):
+    """map_size, map_num_clouds, `inserted` and the BITS of map_points against the model (each message names its check)."""
+    assert ctx.map_size() == len(model), f"[map size] {tag}: map_size {ctx.map_size()}, the model holds {len(model)}"
+    assert ctx.map_num_clouds() == len(model.counts), \
+        f"[num clouds] {tag}: map_num_clouds {ctx.map_num_clouds()}, the model counts {model.counts}"
+    if inserted is not None:
+        assert inserted == model.inserted, f"[inserted] {tag}: inserted {inserted}, the model {model.inserted}"
+    why = first_difference(ctx.map_points(), model.map)
+    assert why is None, f"[map bits] {tag}: the map does not have the model's bits: {why}"
+
+
+def searched(name, i):
+    """Whether the device test runs check_search behind operation i of a script (`drift`: not behind its first 39 moves)."""
+    return name != "drift" or i < 3 or i == len(script(name).ops) - 1
+
+
+def check_search(ctx, model, tag, seed, nref=None):
+    """`nearest_neighbor_search(probes, with_index=True)` of search_probes(map, seed) against the model's map — `seed` is
+    the index of the operation in its script, the rule test_census follows; an empty map raises as
+    test_tiny_maps_and_duplicates expects.  Returns (figures, NormalReference on the model's map, normals by index)."""
+    import pytest
+    if not len(model):
+        with pytest.raises(RuntimeError):
+            ctx.nearest_neighbor_search(np.zeros((2, 3), F32))
+        return None, None, None
+    m = model.map
+    nref = nref or A.NormalReference(m, int(ctx.config.num_neighbors_normals))
+    probes = search_probes(m, seed)
+    nb, nm, ix = ctx.nearest_neighbor_search(probes, with_index=True)
+    fig = verify_search(tag, m, probes, nb, nm, ix, nref, n_self=len(m))
+    normals = np.full((len(m), 3), np.nan, F32)
+    normals[ix] = nm
+    fig["ix"] = ix
+    return fig, nref, normals
+
+
+def check_registration(ctx, model, scan, init, tag, worst=None):
+    """K_REG iterations at threshold 0 of `scan` against the map, the last iteration audited (tests/iteration_audit.py, its
+    own bars) against the map the MODEL says is there and the library's normals of it."""
+    ctx.set_alignment(SCHEME, SIGMA, K_REG, 0.0)
+    rc, res = A.raw_register(ctx, scan, init, True)
+    rec, mp, nm = A.observe(ctx, rc, res, int(np.asarray(scan).shape[0]))
+    assert rec is not None and rec.ix is not None, f"{tag}: the last iteration was not observable"
+    why = first_difference(mp, model.map)
+    assert why is None, f"{tag}: a registration changed the map: {why}"
+    A.audit_run(tag, [rec], scan, model.map, nm, SCHEME, SIGMA, "point_to_plane", True, None, worst, duplicates=True,
+                k_normals=int(ctx.config.num_neighbors_normals))
+    assert ctx.handoff_fallbacks() == 0, tag
+    return rc, res
