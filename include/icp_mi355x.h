@@ -494,7 +494,8 @@ int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
  * ICP_ERR_INVALID_ARGUMENT with a message, the context usable as before: a context that holds a projective map, an exchange or
  * profiling switched on, a context held by a batch, icp_frame_launch before icp_odometry_init or while a frame awaits its
  * icp_frame_end, icp_frame_end with nothing launched.  Single-context entry points between the two calls follow the rules of
- * icp_register_launch.  One frame at a time per context; a batched form (icp_batch_frame_*) does not exist. */
+ * icp_register_launch.  One frame at a time per context; B contexts step together through icp_batch_frame_launch /
+ * icp_batch_frame_end below. */
 typedef struct icp_frame_config {
     double voxel_size;         /* > 0: GridSample (slam/preprocessing.py:207-226) in front of the frame; <= 0: the rows as given */
     float threshold_trans;     /* key-frame test, metres (ICPFrameToModelConfig.threshold_trans, icp_odometry.py:29-64: 0.1) */
@@ -670,6 +671,61 @@ int icp_batch_preprocess(icp_batch* batch, const icp_preprocess_frame* frames, d
 int icp_batch_project_rows(icp_batch* batch, const float* const* xyz, const int64_t* n, float* const* vmap_out,
                            float* const* rows_out);
 int icp_batch_stage(icp_batch* batch, const float* const* xyz, const int64_t* n, int row_mode);
+
+/* ---- one call per odometry frame, B sequences per call -----------------------------------------------------------------
+ * icp_frame_launch / icp_frame_end for the members of a batch: the frame loop of B drives behind two calls, every launch
+ * the batched one of the entry points above.  Per member the calls give what icp_frame_launch / icp_frame_end give on that
+ * member's context alone with the same frames, bit for bit: pose, parameters, iteration count, losses, steps, key-frame
+ * decision, samples, inserted, odometry_pc, map, window and every later frame.  No kernel of its own.
+ *   icp_batch_odometry_init  icp_odometry_init(member, cfg) on every member, every member checked before any is restarted.  The sequence state — motion since the last
+ *                      key frame, last relative pose, frame index, settings — is the MEMBER's: a member may be stepped by
+ *                      the batch, then alone with icp_frame_launch / icp_frame_end, then by the batch again, and may be
+ *                      restarted alone with icp_odometry_init(member, cfg) between two steps.
+ *   icp_batch_frame_launch  frames[b] = member b's next frame (`mem`: where every xyz / timestamps lives).  skip != 0: the
+ *                      member sits this step out — nothing of it is read, enqueued or changed.  The other members fall into
+ *                      two groups.  FIRST FRAME (frame index 0): member by member what icp_frame_launch does for frame 0 (its
+ *                      projection and icp_map_update_vertex_map); no registration.  REGISTERING (frame index >= 1), in
+ *                      icp_frame_launch's order with ONE call per stage for the whole group: the uploads from host arrays,
+ *                      icp_batch_preprocess for a group that grid-samples (members with timestamps and a guess are de-skewed
+ *                      in the same call, the others pass through; icp_frame_launch's rule for the guess; without a grid sample
+ *                      a de-skewed member takes icp_distort's launch and the float32 cast), icp_batch_project_rows
+ *                      (targets = 1), icp_batch_stage, the copies of the staged rows and sample counts towards the host on a
+ *                      stream of the batch's own, and icp_batch_register_launch — from_last = 1 when every registering member
+ *                      would take icp_register_launch_from_last on its own, the host guesses otherwise (the same bits).
+ *                      The batched form always stages: stage_max_rows is not consulted (the same map either way).
+ *                      Host arrays travel through ONE pinned buffer, ONE upload stream and two alternating device buffers of
+ *                      the batch, whatever the member count; odometry_pc through ONE pinned buffer and ONE copy stream.
+ *   icp_batch_frame_end  icp_batch_register_end for the registering group, each member's key-frame test
+ *                      (ICPFrameToModel.__update_map, slam/odometry/icp_odometry.py:360-380, as icp_frame_end applies it), then
+ *                      icp_batch_map_update_staged over the members whose registration succeeded.  results[b] as
+ *                      icp_frame_end fills it; a skipped member's is zeroed with frame_index = -1.  loss_per_iter_out /
+ *                      dx_per_iter_out: count x max_num_alignments (x 6) entries as for icp_batch_register_end, or NULL.
+ *                      odometry_pc_out (NULL, or count pointers of which any may be NULL), cap[b] rows each, rows_out[b]
+ *                      (optional) as for icp_frame_end.
+ * A FAILED REGISTRATION (ICP_ERR_INVALID_JACOBIAN) leaves its member as icp_frame_end leaves a single context: the map
+ * untouched, the sequence not advanced, the device pose given up; every other member completes its frame.  The call returns
+ * the first such status, every member's own is in results[b].reg.status.  cap[b] below the member's row count: the single
+ * call's rule per member — ICP_ERR_INVALID_ARGUMENT, the count in rows_out[b], nothing written for that member, every frame
+ * completed.
+ * REFUSALS, checked for every member before any member changes (ICP_ERR_INVALID_ARGUMENT, icp_batch_last_error names the
+ * member and the reason, nothing enqueued, every sequence where it was): a non-skipped member without a sequence; a launch
+ * while a launch awaits its end; an end with nothing launched; every member skipped; a member that runs point-to-point (the
+ * batch registers point-to-plane only), holds a projective map, an exchange or profiling, is in or awaits a registration or
+ * a frame of its own; non-skipped members that differ in voxel_size or targets (one batched preprocessing and one target
+ * mode per step); members on different streams.  A refusal's message ends in "(nothing was changed)"; every other status of
+ * icp_batch_frame_end comes back behind a completed step.  A frame the batch has launched is ended by the batch: icp_frame_end and
+ * icp_odometry_init on such a member are refused until then. */
+typedef struct icp_batch_frame {
+    const float* xyz;          /* [n,3] float32, host or device (the call's `mem`) */
+    int64_t n;
+    const double* timestamps;  /* [n] float64 where xyz lives, or NULL */
+    const float* init_pose;    /* 16 floats (host) or NULL: as icp_frame_launch */
+    int32_t skip;              /* != 0: this member sits the step out; nothing of it is read, enqueued or changed */
+} icp_batch_frame;
+int icp_batch_odometry_init(icp_batch* batch, const icp_frame_config* cfg);
+int icp_batch_frame_launch(icp_batch* batch, const icp_batch_frame* frames, int mem);
+int icp_batch_frame_end(icp_batch* batch, icp_frame_result* results, float* const* odometry_pc_out, const int64_t* cap,
+                        int64_t* rows_out, int out_mem, double* loss_per_iter_out, float* dx_per_iter_out);
 
 /* ---- multi-GPU exchange inside the library ("one-shot P2P write+flag all-reduce") -----------------
  * The per-iteration exchange of the scan-sharded registration without leaving the library: after these three calls

@@ -1981,28 +1981,7 @@ int icp_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_
 // all iterations of all members first: nothing in it depends on a launch having been issued), travel to the device in one
 // copy, and the launches follow.  Three slots in rotation: a slot is rewritten when the registration two frames back has been
 // collected (at most two registrations are ever pending per member), so its launches have long finished.
-struct icp_batch {
-    std::vector<icp_ctx*> members;
-    std::string error;
-    int device = 0;
-    static constexpr int SLOTS = 3;
-    char* host[SLOTS] = {nullptr, nullptr, nullptr};  // pinned
-    size_t host_bytes[SLOTS] = {0, 0, 0};
-    DeviceBuffer dev[SLOTS];
-    hipEvent_t copied[SLOTS] = {nullptr, nullptr, nullptr};  // the slot's copy has left the pinned buffer
-    hipEvent_t done[2] = {nullptr, nullptr};                  // ONE event behind the results of a batched registration
-    int slot = 0, done_next = 0;
-    // the registration in progress: iterations [run_next, run_iters) are still held back (a live stop threshold: chunks)
-    bool run_active = false, run_lead = false;
-    int run_next = 0, run_iters = 0, run_done = 0;
-    int run_prev_rows[ICP_BATCH_MAX_SEQUENCES] = {}, run_prev_quad[ICP_BATCH_MAX_SEQUENCES] = {};
-    // ... and of the batched grid build behind a map update: [count] GridBuildDesc per slot (then, for
-    // icp_batch_map_update_staged, ICP_BATCH_MAX_SEQUENCES NormalsBatchDesc: the eager normals of the same update)
-    GridBuildDesc* grid_host[SLOTS] = {nullptr, nullptr, nullptr};
-    DeviceBuffer grid_dev[SLOTS];
-    hipEvent_t grid_copied[SLOTS] = {nullptr, nullptr, nullptr};
-    int grid_slot = 0;
-};
+// (struct icp_batch: icp_internal.h — batch_frame.hip composes the entry points below over subsets of its members)
 
 static int batch_fail(icp_batch* b, int code, const std::string& msg) {
     if (b) b->error = msg;
@@ -2040,6 +2019,7 @@ int icp_batch_create(icp_ctx* const* ctxs, int32_t count, icp_batch** out) {
 void icp_batch_destroy(icp_batch* b) {
     if (!b) return;
     DeviceGuard device_guard(b->device);
+    batch_frames_release(b);  // (a step launched and never ended is collected and dropped; the inner batches of partial steps)
     (void)hipDeviceSynchronize();  // (launches that read the tables; members whose result slots wait for the batch's events)
     for (icp_ctx* ctx : b->members) {
         ctx->batch_hold = false;  // (iterations the batch still held back are dropped: the members' results stand as they are)

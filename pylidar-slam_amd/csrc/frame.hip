@@ -4,41 +4,11 @@
 #include <string.h>
 
 #include "frame_keyframe.h"
+#include "frame_loop.h"
 #include "icp_internal.h"
 
 using namespace icp;
 
-struct icp_frame_loop {
-    icp_frame_config cfg;
-    int32_t index = 0;      // frames completed since icp_odometry_init
-    bool launched = false;  // a frame awaits its icp_frame_end
-    bool registered = false;  // ... with a registration enqueued (false: frame 0)
-    float delta[16];        // `_delta_since_map_update`
-    float last_pose[16];    // the last relative pose (the constant-velocity guess)
-    long long pose_epoch = -1;  // ctx->device_pose_epoch behind the last frame's launch: while it stands, the device pose is that frame's
-    // ---- input: pinned staging -> one of two device slots, on a stream of its own (odometry.py::_upload)
-    void* pin_in = nullptr;
-    size_t pin_in_bytes = 0;
-    hipEvent_t pin_in_free = nullptr;
-    bool pin_in_busy = false;
-    DeviceBuffer slot[2];
-    int which = 0;
-    hipStream_t upload_stream = nullptr;
-    // ---- the frame on the device
-    DeviceBuffer skew64, samp64, samp32, vmap, rows, count;
-    const float* frame_rows = nullptr;  // [n,3] float32: what is staged, projected and (targets = 0) registered
-    int64_t n = 0;
-    bool sampled = false;
-    bool staged = false;    // the frame's valid rows were compacted in front of its registration
-    int64_t inserted0 = 0;  // frame 0's insertion
-    // ---- odometry_pc: the staged rows towards pinned memory, beside the registration
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t copy_done = nullptr;
-    void* pin_out = nullptr;
-    size_t pin_out_bytes = 0;
-    int* pin_count = nullptr;  // the grid sample's count
-    bool copy_started = false;
-};
 
 namespace {
 
@@ -112,6 +82,18 @@ void frame_drop_pending(icp_ctx* ctx, icp_frame_loop* f) {
 
 namespace icp {
 
+// what icp_odometry_init refuses, nothing changed (icp_batch_odometry_init asks every member first; own_batch: the frame a
+// batch has launched on the context is that batch's own step, which it drops itself)
+int frame_init_check(icp_ctx* ctx, const icp_frame_config* cfg, bool own_batch) {
+    int rc = frame_refusals(ctx, "icp_odometry_init");
+    if (rc) return rc;
+    if ((cfg->targets != 0 && cfg->targets != 1) || !(cfg->threshold_trans >= 0.f) || !(cfg->threshold_rot >= 0.f))
+        return frame_fail(ctx, "icp_odometry_init: targets is 0 or 1, the key-frame thresholds are not negative");
+    if (!own_batch && ctx->frame && ctx->frame->launched && ctx->frame->batched)
+        return frame_fail(ctx, "icp_odometry_init: a frame launched by a batch awaits icp_batch_frame_end");
+    return ICP_OK;
+}
+
 void frame_loop_release(icp_ctx* ctx) {
     icp_frame_loop* f = ctx ? ctx->frame : nullptr;
     if (!f) return;
@@ -147,10 +129,8 @@ void icp_default_frame_config(icp_frame_config* cfg) {
 int icp_odometry_init(icp_ctx* ctx, const icp_frame_config* cfg) {
     if (!ctx || !cfg) return ICP_ERR_INVALID_ARGUMENT;
     DeviceGuard device_guard(ctx, false);  // (the entry points composed below join the map stream where they must)
-    int rc = frame_refusals(ctx, "icp_odometry_init");
+    int rc = frame_init_check(ctx, cfg, false);
     if (rc) return rc;
-    if ((cfg->targets != 0 && cfg->targets != 1) || !(cfg->threshold_trans >= 0.f) || !(cfg->threshold_rot >= 0.f))
-        return frame_fail(ctx, "icp_odometry_init: targets is 0 or 1, the key-frame thresholds are not negative");
     if (!ctx->frame) ctx->frame = new icp_frame_loop();
     icp_frame_loop* f = ctx->frame;
     frame_drop_pending(ctx, f);
@@ -176,14 +156,26 @@ int icp_frame_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, const d
         return frame_fail(ctx, "icp_frame_launch: [n,3] rows in host or device memory are required");
     if (ctx->in_registration || ctx->result_pending())
         return frame_fail(ctx, "icp_frame_launch: a registration of this context is in progress or awaits icp_register_end");
-    const icp_frame_config& c = f->cfg;
-    // ---- the initial guess (ConstantVelocityInitialization, slam/initialization.py:103-119)
-    const bool have_guess = init_pose != nullptr || c.constant_velocity != 0;
-    const float* guess = init_pose ? init_pose : f->last_pose;  // (identity without constant_velocity: see below)
     // ---- input
     const float* rows = xyz;
     const double* ts = timestamps;
     if (n > 0 && mem == ICP_MEM_HOST && (rc = frame_upload(ctx, f, xyz, timestamps, n, &rows, &ts))) return rc;
+    return frame_launch_device(ctx, rows, n, ts, init_pose);
+}
+
+}  // extern "C"
+
+namespace icp {
+
+// icp_frame_launch behind its checks and its upload: rows / ts in device memory (icp_batch_frame_launch runs the first frame
+// of a member through here, behind the batch's own upload)
+int frame_launch_device(icp_ctx* ctx, const float* rows, int64_t n, const double* ts, const float init_pose[16]) {
+    icp_frame_loop* f = ctx->frame;
+    int rc;
+    const icp_frame_config& c = f->cfg;
+    // ---- the initial guess (ConstantVelocityInitialization, slam/initialization.py:103-119)
+    const bool have_guess = init_pose != nullptr || c.constant_velocity != 0;
+    const float* guess = init_pose ? init_pose : f->last_pose;  // (identity without constant_velocity: see below)
     // ---- de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126)
     const bool skew = n > 0 && ts != nullptr && have_guess;
     const bool sample = n > 0 && c.voxel_size > 0;
@@ -288,6 +280,10 @@ int icp_frame_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, const d
     return ICP_OK;
 }
 
+}  // namespace icp
+
+extern "C" {
+
 int icp_frame_end(icp_ctx* ctx, icp_frame_result* result, float* odometry_pc_out, int64_t cap, int64_t* rows_out,
                   int out_mem, double* loss_per_iter_out, float* dx_per_iter_out) {
     if (!ctx || !result) return ICP_ERR_INVALID_ARGUMENT;
@@ -295,6 +291,7 @@ int icp_frame_end(icp_ctx* ctx, icp_frame_result* result, float* odometry_pc_out
     icp_frame_loop* f = ctx->frame;
     if (!f || !f->launched) return frame_fail(ctx, "icp_frame_end: no frame launched (icp_frame_launch first)");
     if (ctx->batch_hold) return frame_fail(ctx, "icp_frame_end: the context is held by a batched registration");
+    if (f->batched) return frame_fail(ctx, "icp_frame_end: the frame was launched by a batch (icp_batch_frame_end ends it)");
     if (odometry_pc_out && cap < 0) return frame_fail(ctx, "icp_frame_end: negative capacity");
     memset(result, 0, sizeof(*result));
     result->frame_index = f->index;

@@ -614,6 +614,32 @@ struct icp_ctx {
     struct icp_frame_loop* frame = nullptr;    // created by icp_odometry_init, released by icp_destroy (frame_loop_release)
 };
 
+// ---- B sequences per launch (api.hip: icp_batch_*)
+struct icp_batch {
+    std::vector<icp_ctx*> members;
+    std::string error;
+    int device = 0;
+    static constexpr int SLOTS = 3;
+    char* host[SLOTS] = {nullptr, nullptr, nullptr};  // pinned
+    size_t host_bytes[SLOTS] = {0, 0, 0};
+    icp::DeviceBuffer dev[SLOTS];
+    hipEvent_t copied[SLOTS] = {nullptr, nullptr, nullptr};  // the slot's copy has left the pinned buffer
+    hipEvent_t done[2] = {nullptr, nullptr};                  // ONE event behind the results of a batched registration
+    int slot = 0, done_next = 0;
+    // the registration in progress: iterations [run_next, run_iters) are still held back (a live stop threshold: chunks)
+    bool run_active = false, run_lead = false;
+    int run_next = 0, run_iters = 0, run_done = 0;
+    int run_prev_rows[ICP_BATCH_MAX_SEQUENCES] = {}, run_prev_quad[ICP_BATCH_MAX_SEQUENCES] = {};
+    // ... and of the batched grid build behind a map update: [count] GridBuildDesc per slot (then, for
+    // icp_batch_map_update_staged, ICP_BATCH_MAX_SEQUENCES NormalsBatchDesc: the eager normals of the same update)
+    icp::GridBuildDesc* grid_host[SLOTS] = {nullptr, nullptr, nullptr};
+    icp::DeviceBuffer grid_dev[SLOTS];
+    hipEvent_t grid_copied[SLOTS] = {nullptr, nullptr, nullptr};
+    int grid_slot = 0;
+    // ---- one call per odometry frame for the batch (batch_frame.hip: icp_batch_frame_launch / icp_batch_frame_end)
+    struct icp_batch_frames* frames = nullptr;  // created by the first batched frame call, released by icp_batch_destroy
+};
+
 namespace icp {
 
 #define ICP_HIP(ctx, expr)                                                                          \
@@ -632,6 +658,8 @@ inline int fail(icp_ctx* ctx, int code, const char* msg) {
 
 // ---- frame.hip
 void frame_loop_release(icp_ctx* ctx);
+// ---- batch_frame.hip
+void batch_frames_release(icp_batch* batch);
 
 // ---- hash_grid.hip
 // defer != nullptr: everything but the launches — *defer receives their arguments (the caller launches them, e.g. for B maps

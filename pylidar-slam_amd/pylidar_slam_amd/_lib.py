@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpFrameResult", "load_library", "library_path",
+__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpFrameResult", "IcpBatchFrame", "load_library", "library_path",
            "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -75,6 +75,12 @@ class IcpFrameResult(C.Structure):
     """icp_frame_result: what icp_frame_end returns for one frame."""
     _fields_ = [("reg", IcpRegisterResult), ("frame_index", C.c_int32), ("key_frame", C.c_int32),
                 ("samples", C.c_int64), ("inserted", C.c_int64)]
+
+
+class IcpBatchFrame(C.Structure):
+    """icp_batch_frame: one member's frame of icp_batch_frame_launch."""
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_int64), ("timestamps", C.c_void_p), ("init_pose", C.c_void_p),
+                ("skip", C.c_int32)]
 
 
 _P = C.c_void_p
@@ -158,6 +164,9 @@ EXPORTED_SYMBOLS = {
     "icp_batch_preprocess": (_INT, [_P, C.POINTER(IcpPreprocessFrame), C.c_double]),
     "icp_batch_project_rows": (_INT, [_P, _P, _P, _P, _P]),
     "icp_batch_stage": (_INT, [_P, _P, _P, _INT]),
+    "icp_batch_odometry_init": (_INT, [_P, C.POINTER(IcpFrameConfig)]),
+    "icp_batch_frame_launch": (_INT, [_P, C.POINTER(IcpBatchFrame), _INT]),
+    "icp_batch_frame_end": (_INT, [_P, C.POINTER(IcpFrameResult), _P, _P, _P, _INT, _P, _P]),
     "icp_normal_equations_ptr": (_P, [_P]),
     "icp_set_normal_equations_buffer": (_INT, [_P, _P]),
     "icp_profile_enable": (_INT, [_P, _INT]),

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (COSTS, IcpConfig, IcpFrameConfig, IcpFrameResult, IcpLibraryError, IcpPreprocessFrame,
+from ._lib import (COSTS, IcpBatchFrame, IcpConfig, IcpFrameConfig, IcpFrameResult, IcpLibraryError, IcpPreprocessFrame,
                    IcpRegisterResult, MEM_DEVICE, MEM_HOST, SCHEMES, STATUS_MESSAGES, TARGETS_ALL, TARGETS_SKIP_NULL)
 
 Array = Union[np.ndarray, torch.Tensor]
@@ -79,6 +79,22 @@ def _ptr_mem(a: Optional[Array]) -> Tuple[Optional[int], int, object]:
 
 def _on_device(*arrays) -> bool:
     return any(isinstance(a, torch.Tensor) and a.is_cuda for a in arrays)
+
+
+_FRAME_CONFIG_FIELDS = {"voxel_size": float, "threshold_trans": float, "threshold_rot": float,
+                        "constant_velocity": lambda v: int(bool(v)), "targets": int, "copy_cloud": lambda v: int(bool(v)),
+                        "stage_max_rows": int}
+
+
+def _frame_config(lib, **kw) -> IcpFrameConfig:
+    """icp_default_frame_config with the given fields set (`IcpContext.odometry_init` and `IcpBatch.odometry_init`)."""
+    cfg = IcpFrameConfig()
+    lib.icp_default_frame_config(C.byref(cfg))
+    for k, v in kw.items():
+        if k not in _FRAME_CONFIG_FIELDS:
+            raise TypeError(f"odometry_init() got an unexpected keyword argument {k!r}")
+        setattr(cfg, k, _FRAME_CONFIG_FIELDS[k](v))
+    return cfg
 
 
 def _pose16(m) -> "C.Array":
@@ -741,12 +757,14 @@ class IcpContext:
         map; constant_velocity: the initial guess of a frame is the last relative pose; copy_cloud: `frame_end` returns the
         frame's valid rows (`odometry_pc`), copied beside the registration; stage_max_rows: larger raw frames are not
         compacted in front of their registration (see icp_frame_config)."""
-        cfg = IcpFrameConfig()
-        self._lib.icp_default_frame_config(C.byref(cfg))
-        cfg.voxel_size, cfg.threshold_trans, cfg.threshold_rot = float(voxel_size), float(threshold_trans), float(threshold_rot)
-        cfg.constant_velocity, cfg.targets, cfg.copy_cloud = int(bool(constant_velocity)), int(targets), int(bool(copy_cloud))
-        cfg.stage_max_rows = int(stage_max_rows)
+        cfg = _frame_config(self._lib, voxel_size=voxel_size, threshold_trans=threshold_trans, threshold_rot=threshold_rot,
+                            constant_velocity=constant_velocity, targets=targets, copy_cloud=copy_cloud,
+                            stage_max_rows=stage_max_rows)
         self._check(self._lib.icp_odometry_init(self._h, C.byref(cfg)))
+        self._sequence_started(cfg)
+
+    def _sequence_started(self, cfg: IcpFrameConfig):
+        """A sequence of frame calls has been started on this context (by `odometry_init`, here or on a batch)."""
         self._frame_cfg = cfg
         self._frame_keep = None
         self._frame_rows = 0
@@ -1130,6 +1148,128 @@ class IcpBatch:
         vm = (C.c_void_p * b)(*ptrs)
         self._keep_vmaps = keep  # (alive until the next update: the copies _planar made are read by the enqueued launches)
         self._check(self._lib.icp_batch_pmap_update(self._h, rel.ctypes.data, vm, mem, int(normals_kernel_size)))
+
+    # ---- one call per odometry frame, B sequences per call -------------------------------------------------------------
+    def odometry_init(self, **kw):
+        """`icp_batch_odometry_init`: `IcpContext.odometry_init(**kw)` on every member (the sequence state is the member's
+        own: a member may also be stepped, or restarted, alone)."""
+        cfg = _frame_config(self._lib, **kw)
+        self._check(self._lib.icp_batch_odometry_init(self._h, C.byref(cfg)))
+        for c in self.contexts:
+            mine = IcpFrameConfig()
+            C.memmove(C.byref(mine), C.byref(cfg), C.sizeof(cfg))
+            c._sequence_started(mine)
+        self._frame_step = None
+
+    def frame_launch(self, scans, timestamps=None, init_poses=None, skip=None):
+        """`icp_batch_frame_launch`: `scans[b]` = member b's next frame ([N,3] float32; all numpy arrays — uploaded by the
+        library through ONE pinned buffer — or all cuda tensors, used in place until `frame_end`); `timestamps[b]` ([N]
+        float64 where the points live) or None; `init_poses[b]` (4x4) or None; `skip[b]`: the member sits this step out
+        (its scan may be None)."""
+        b = len(self.contexts)
+        skip = [False] * b if skip is None else [bool(v) for v in skip]
+        timestamps = [None] * b if timestamps is None else list(timestamps)
+        init_poses = [None] * b if init_poses is None else list(init_poses)
+        if len(scans) != b or len(skip) != b or len(timestamps) != b or len(init_poses) != b:
+            raise AssertionError(f"expected {b} scans, timestamps, initial poses and skip flags")
+        active = [a for a, sk in zip(scans, skip) if not sk]
+        on_device = bool(active) and all(isinstance(a, torch.Tensor) and a.is_cuda for a in active)
+        if not on_device and _on_device(*active):
+            raise AssertionError("the frames of a batched step must live in one memory space")
+        if on_device:
+            self.use_torch_stream()
+        frames = (IcpBatchFrame * b)()
+        keep, rows = [], [0] * b
+        for i, (a, t, g, sk) in enumerate(zip(scans, timestamps, init_poses, skip)):
+            f = frames[i]
+            f.skip = 1 if sk else 0
+            if sk:
+                continue
+            if on_device:
+                pts = a if a.dtype == torch.float32 and a.is_contiguous() else a.to(torch.float32).contiguous()
+                ts = None if t is None else torch.as_tensor(t).to(pts.device, torch.float64).reshape(-1).contiguous()
+                ptr, tptr = pts.data_ptr(), (ts.data_ptr() if ts is not None else None)
+            else:
+                pts = a.numpy() if isinstance(a, torch.Tensor) else a
+                if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.flags.c_contiguous):
+                    pts = np.ascontiguousarray(pts, dtype=np.float32)
+                ts = None if t is None else np.ascontiguousarray(np.asarray(t).reshape(-1), dtype=np.float64)
+                ptr, tptr = pts.ctypes.data, (ts.ctypes.data if ts is not None else None)
+            if pts.ndim != 2 or pts.shape[1] != 3 or (ts is not None and ts.shape[0] != pts.shape[0]):
+                raise AssertionError(f"member {i}: expected [N,3] points (and [N] timestamps), got {tuple(pts.shape)}")
+            n = int(pts.shape[0])
+            pose = _pose16(g) if g is not None else None
+            f.xyz, f.n, f.timestamps = (ptr if n else None), n, (tptr if n else None)
+            f.init_pose = C.cast(pose, C.c_void_p) if pose is not None else None
+            keep.append((pts, ts, pose))
+            rows[i] = n
+        self._check(self._lib.icp_batch_frame_launch(self._h, frames, MEM_DEVICE if on_device else MEM_HOST))
+        self._frame_step = (keep if on_device else None, rows, skip)
+
+    def frame_end(self, with_points=None, cap=None):
+        """`icp_batch_frame_end`: one wait for all registrations, the key-frame tests, one batched map update.  A list with
+        one `FrameResult` per member (None: the member sat the step out).  with_points: a flag or one per member (default:
+        each member's `copy_cloud`).  A member whose registration failed raises `InvalidJacobianError` AFTER the step has
+        completed for the others — `.results` (None at the failed positions) and `.failed`, as `register_end`; a `cap[b]`
+        below the member's rows raises AssertionError with `.results` (that member's `points` None) and `.rows`."""
+        b = len(self.contexts)
+        step = getattr(self, "_frame_step", None)
+        rows = step[1] if step else [0] * b
+        skip = step[2] if step else [False] * b
+        if with_points is None:
+            want = [bool(getattr(c, "_frame_cfg", None) is not None and c._frame_cfg.copy_cloud) for c in self.contexts]
+        elif isinstance(with_points, (list, tuple)):
+            want = [bool(v) for v in with_points]
+        else:
+            want = [bool(with_points)] * b
+        caps = [int(r) for r in rows] if cap is None else [int(v) for v in cap]
+        hist = max(1, int(self.contexts[0].config.max_num_alignments))
+        res = (IcpFrameResult * b)()
+        losses = (C.c_double * (hist * b))()
+        dxs = (C.c_float * (6 * hist * b))()
+        outs = [np.empty((max(c, 1), 3), np.float32) if (w and not sk) else None for c, w, sk in zip(caps, want, skip)]
+        out_ptrs = (C.c_void_p * b)(*[o.ctypes.data if o is not None else None for o in outs])
+        cap_arr = (C.c_int64 * b)(*caps)
+        counts = (C.c_int64 * b)()
+        rc = self._lib.icp_batch_frame_end(self._h, res, out_ptrs, cap_arr, counts, MEM_HOST, losses, dxs)
+        if rc == _lib.ICP_ERR_INVALID_ARGUMENT and \
+                self._lib.icp_batch_last_error(self._h).decode().endswith("(nothing was changed)"):
+            self._check(rc)  # refused: the step (if any) still awaits its end
+        self._frame_step = None
+        la = np.array(losses, np.float64).reshape(b, hist)
+        da = np.array(dxs, np.float32).reshape(b, hist, 6)
+        out, failed = [], []
+        for i in range(b):
+            r = res[i]
+            if int(r.frame_index) < 0:
+                out.append(None)
+                continue
+            if int(r.reg.status) != 0:
+                failed.append(i)
+                out.append(None)
+                continue
+            k = int(r.reg.iterations)
+            reg = RegisterResult(np.array(r.reg.pose, np.float32).reshape(4, 4), np.array(r.reg.params, np.float32), k,
+                                 bool(r.reg.converged), int(r.reg.num_targets), int(r.reg.normals_computed),
+                                 la[i, :k].copy(), da[i, :k].copy())
+            first = int(r.frame_index) == 0
+            n = int(counts[i])
+            pts = outs[i][:n] if (outs[i] is not None and not first and n <= caps[i]) else None
+            out.append(FrameResult(reg, int(r.frame_index), bool(r.key_frame), int(r.samples), int(r.inserted), pts))
+        if rc != 0:
+            try:
+                self._check(rc)
+            except Exception as err:
+                err.results, err.failed, err.rows = out, failed, [int(v) for v in counts]
+                if failed:  # (what the registration reached, as IcpContext.frame_end hands it over)
+                    i = failed[0]
+                    k = int(res[i].reg.iterations)
+                    err.result = RegisterResult(np.array(res[i].reg.pose, np.float32).reshape(4, 4),
+                                                np.array(res[i].reg.params, np.float32), k, bool(res[i].reg.converged),
+                                                int(res[i].reg.num_targets), int(res[i].reg.normals_computed),
+                                                la[i, :k].copy(), da[i, :k].copy())
+                raise
+        return out
 
     def register_end(self):
         """One wait for all members; a list of `RegisterResult`s.  Raises what the first failing member would raise; the

@@ -929,7 +929,9 @@ class MI355XICPConfig:
     compact_sparse_vertex_map: bool = False
     # True: a frame is ONE pair of library calls (icp_frame_launch + icp_frame_end, include/icp_mi355x.h) instead of the ten
     # calls of do_process_next_frame below — the same poses, iterations, insertions and map, bit for bit.  numpy [N, 3] and
-    # cuda [N, 3] frames against the kd-tree style map; anything else is refused with the reason, not routed elsewhere
+    # cuda [N, 3] frames against the kd-tree style map; anything else is refused with the reason, not routed elsewhere.
+    # `MI355XICPFrameToModelBatch`: a step of all members is ONE pair of calls (icp_batch_frame_launch + icp_batch_frame_end),
+    # and numpy [N, 3] frames are accepted on that route
     one_call_frame: bool = False
 
 
@@ -1361,7 +1363,10 @@ class MI355XICPFrameToModelBatch:
     `_read_input` runs per member.  [3,H,W] / [1,3,H,W] vertex maps take `_read_input` per member.  `MI355XPreprocessingBatch`
     prepares the B frames in front of it in one call.
 
-    Input: torch tensors (device-resident preprocessing, or [3,H,W] / [1,3,H,W] vertex maps)."""
+    Input: torch tensors (device-resident preprocessing, or [3,H,W] / [1,3,H,W] vertex maps).
+
+    `MI355XICPConfig.one_call_frame=True` (kd-tree style map): the step goes through `IcpBatch.frame_launch` / `frame_end`
+    instead (`_process_one_call`): numpy [N, 3] or cuda [N, 3] frames, the same poses, clouds and maps, bit for bit."""
 
     def __init__(self, config: MI355XICPConfig, count: int, projector=None, device=None, **kwargs):
         assert_debug(int(count) >= 1, "a batch needs at least one sequence")
@@ -1374,6 +1379,14 @@ class MI355XICPFrameToModelBatch:
         self.device = m0.device
         self._iter = 0
         self.elapsed: list = []
+        # `one_call_frame`: a step is ONE pair of library calls for all members (icp_batch_frame_launch + icp_batch_frame_end)
+        # instead of the calls of _process below.  The members were built with the flag, so each has already refused what the
+        # frame calls do not cover (the projective map, compact_sparse_vertex_map); here they are only containers of the
+        # sequences' outputs
+        self._one_call = bool(_get(self.config, "one_call_frame", False))
+        self._one_call_targets = None
+        if self._one_call:
+            assert_debug(hasattr(self.batch, "frame_launch"), "one_call_frame needs the library's batched frame calls")
 
     def __len__(self):
         return len(self.members)
@@ -1395,8 +1408,89 @@ class MI355XICPFrameToModelBatch:
         its initial estimate under `init_rpose` as for the single plugin); fills `odometry_pose` and `odometry_pc` of every
         dict, as MI355XICPFrameToModel.process_next_frame does."""
         beginning = time.time()
-        self._process(data_dicts)
+        if self._one_call:
+            self._process_one_call(data_dicts)
+        else:
+            self._process(data_dicts)
         self.elapsed.append(time.time() - beginning)
+
+    def _process_one_call(self, data_dicts):
+        """`one_call_frame`: the step through icp_batch_frame_launch + icp_batch_frame_end — per member what
+        `MI355XICPFrameToModel._one_call_next_frame` does with icp_frame_launch + icp_frame_end: the library uploads numpy
+        frames (ONE pinned buffer and ONE copy for all members), projects, stages, registers from every dict's `init_rpose`,
+        applies the key-frame tests and updates the maps; what stays here are the pose chains and the dicts' outputs.  numpy
+        [N, 3] frames (not accepted on the per-call path) and cuda [N, 3] frames.  A member whose registration fails raises
+        `InvalidJacobianError` after the other members have completed their frame (their dicts and pose lists are filled)."""
+        members = self.members
+        assert_debug(len(data_dicts) == len(members), f"expected {len(members)} frames, got {len(data_dicts)}")
+        key = self.config.data_key
+        for d in data_dicts:
+            assert_debug(key in d, f"Could not find the key `{key}` in the input dictionary.")
+        frames = [d[key] for d in data_dicts]
+        is_numpy = all(isinstance(f, np.ndarray) for f in frames)
+        assert_debug(is_numpy or all(isinstance(f, torch.Tensor) and f.is_cuda and f.ndim == 2 for f in frames),
+                     "one_call_frame covers numpy [N, 3] and cuda [N, 3] frames (all members alike): a vertex-map tensor (or a "
+                     "cpu tensor) goes through the per-call path (one_call_frame=False), got "
+                     f"{[(type(f).__name__, tuple(getattr(f, 'shape', ()))) for f in frames]}")
+        for f in frames:
+            assert_debug(f.ndim == 2 and f.shape[1] == 3, f"expected [N, 3], got {tuple(f.shape)}")
+        if is_numpy:
+            for m in members:
+                m._sample_pointcloud = True  # sticky (:330)
+        targets = 0 if members[0]._sample_pointcloud else 1  # sample_points :301-308
+        want = ["distorted" not in d for d in data_dicts]  # (:210-213)
+        first = self._iter == 0
+        if first:
+            self.batch.use_torch_stream()
+            self.batch.odometry_init(voxel_size=0.0, threshold_trans=members[0]._register_threshold_trans,
+                                     threshold_rot=members[0]._register_threshold_rot, constant_velocity=False,
+                                     targets=targets, copy_cloud=any(want) and not is_numpy,
+                                     # (`_one_call_next_frame`'s rule; the batched calls stage every frame whatever it says)
+                                     stage_max_rows=0 if any(d.get("sample_count", None) is not None for d in data_dicts) else
+                                     int(_get(self.config, "stage_insert_max_rows", 32768)))
+            self._one_call_targets = targets
+        assert_debug(targets == self._one_call_targets, "one_call_frame: numpy and tensor frames were mixed within one "
+                                                        "sequence (the targets of a sequence are its rows or its pixels)")
+        if is_numpy:
+            frames = [f if f.dtype == np.float32 and f.flags.c_contiguous else np.ascontiguousarray(f, dtype=np.float32)
+                      for f in frames]
+        else:
+            self.batch.use_torch_stream()
+        self.batch.frame_launch(frames, None, None if first else [m._initial_pose(d) for m, d in zip(members, data_dicts)])
+        pcs = [None] * len(members)
+        if is_numpy and not first:  # (`odometry_pc` of a numpy frame is made from the host rows: GPU busy meanwhile)
+            for b, (m, f, w) in enumerate(zip(members, frames, want)):
+                m._host_rows = f
+                pcs[b] = m._rows_to_host(None) if w else None
+        error = None
+        try:
+            results = self.batch.frame_end(with_points=[w and not is_numpy and not first for w in want])
+        except InvalidJacobianError as e:  # (raised behind the step: the healthy members have completed their frame)
+            error, results = e, e.results
+        for b, (m, res, d) in enumerate(zip(members, results, data_dicts)):
+            if res is None:
+                continue
+            if first:
+                m.relative_poses.append(np.eye(4, dtype=np.float32)[None])
+                m.absolute_poses.append(np.eye(4, dtype=np.float64))
+                m._iter += 1
+                continue
+            m.last_result = res.register
+            pose, params = res.register.pose, res.register.params
+            m._delta_since_map_update = np.eye(4, dtype=np.float32) if res.key_frame else \
+                (m._delta_since_map_update @ pose).astype(np.float32)
+            if res.key_frame:
+                m.local_map._last_count = res.inserted
+            m.relative_poses.append(pose[None].copy())
+            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64), np.float64)))
+            if want[b] and not is_numpy:
+                pcs[b] = res.points.copy()
+            d[m.pointcloud_key()] = pcs[b] if want[b] else d["distorted"]  # :243
+            d[m.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+            m._iter += 1
+        self._iter += 1
+        if error is not None:
+            raise error
 
     def _process(self, data_dicts):
         members = self.members
