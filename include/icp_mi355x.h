@@ -727,6 +727,113 @@ int icp_batch_frame_launch(icp_batch* batch, const icp_batch_frame* frames, int 
 int icp_batch_frame_end(icp_batch* batch, icp_frame_result* results, float* const* odometry_pc_out, const int64_t* cap,
                         int64_t* rows_out, int out_mem, double* loss_per_iter_out, float* dx_per_iter_out);
 
+/* ---- one call per odometry frame against the projective local map (PF2M) --------------------------------------------------
+ * ICPFrameToModel.do_process_next_frame (slam/odometry/icp_odometry.py:157-246) with `ProjectiveLocalMap`
+ * (slam/odometry/local_map.py:113-235) behind two calls, as icp_frame_launch / icp_frame_end give it for the kd-tree style map:
+ * the calls compose the entry points above in the order pylidar_slam_amd/odometry.py::MI355XICPFrameToModel issues them for a
+ * projective map — per frame the same pose, parameters, iteration count, losses, steps, key-frame decision, odometry_pc, window
+ * and model, bit for bit.  Entry points, a config struct and a sequence state of their own: icp_odometry_init and
+ * icp_frame_config know nothing of the projective map.
+ *   icp_pmap_register_launch  icp_pmap_register (register_new_frame :248-299 against ProjectiveLocalMap.nearest_neighbor_search,
+ *                      local_map.py:205-235), enqueued: begin + every iteration on the context's stream, the result copied to
+ *                      pinned memory behind the last one and collected by icp_register_end.  The stop (threshold_delta_pose) is
+ *                      decided on the device — the kernels of an iteration behind it return at once — and the host polls
+ *                      nothing.  Pose, parameters, iterations, losses, steps and status are those of icp_pmap_register, bit for
+ *                      bit.  One registration at a time (ICP_ERR_INVALID_ARGUMENT while one is in progress or awaits
+ *                      icp_register_end).  Every iteration is on the stream when the call returns, so entry points called before
+ *                      icp_register_end run in call order behind it, as icp_register_launch documents; those that need the
+ *                      registration's outcome on the host (icp_pmap_update takes the pose) come after icp_register_end.
+ *   icp_pmap_odometry_init  ICPFrameToModel.init (:128-145): icp_pmap_init, frame counter 0, the motion since the last key frame
+ *                      and the last relative pose = identity.  Calling it again starts a new sequence on the same context (a
+ *                      frame launched and not ended is collected and dropped).
+ *   icp_pmap_frame_launch  enqueues one frame and returns without waiting.  `layout`:
+ *                      ICP_FRAME_ROWS  data = [n,3] float32 rows in host or device memory (`mem`), timestamps [n] float64 where
+ *                      the rows live: the chain of icp_frame_launch — upload through the pinned buffer and two device slots,
+ *                      de-skew by the guess (icp_distort), grid sample (voxel_size > 0) and float32 cast — then the projection
+ *                      (_read_input :319-358).  targets = 1: icp_project_rows, the targets are the pixels of the vertex map
+ *                      with ICP_TARGETS_SKIP_NULL (sample_points :301-308); targets = 0: the targets are the frame's rows, and
+ *                      the vertex map (which only a key frame's insertion reads) is projected BEHIND the registration.
+ *                      ICP_FRAME_VERTEX_MAP  data = a [3,H,W] float32 vertex map in DEVICE memory, n = H*W (the reference's
+ *                      default data_key, :319-344): the targets are its pixels with ICP_TARGETS_SKIP_NULL, transposed to rows
+ *                      by one launch; timestamps or voxel_size > 0 are refused with this layout.  A device input must stay
+ *                      untouched until icp_pmap_frame_end has returned.
+ *                      FRAME 0  icp_pmap_update(identity, vertex map) (:176); no registration.
+ *                      LATER FRAMES  the frame's valid rows are compacted and counted for odometry_pc (rows with a NaN dropped,
+ *                      :357; vertex-map input: null pixels dropped as well, :342-344; input order kept), copied towards pinned
+ *                      memory on a stream of the context's own (copy_cloud) beside the registration, and the registration is
+ *                      enqueued (icp_pmap_register_launch) from init_pose, or the last relative pose under constant_velocity,
+ *                      or the identity.
+ *   icp_pmap_frame_end  icp_register_end: an error status (ICP_ERR_INVALID_JACOBIAN) is returned before the map or the sequence
+ *                      state moves (:286).  Then __update_map (:360-380): the key-frame test of icp_frame_end, unchanged;
+ *                      icp_pmap_update with the frame's vertex map for a key frame (local_map.py:122-174), pose-only
+ *                      otherwise — enqueued, not waited for.  result->inserted = 1 when a vertex map was appended, else 0;
+ *                      samples, odometry_pc_out, cap, *rows_out, loss_per_iter_out, dx_per_iter_out as for icp_frame_end.
+ * ICP_ERR_INVALID_ARGUMENT with a message, the context usable as before: a context whose cost is point-to-point, an exchange or
+ * profiling switched on, a context held by a batch, a kd-tree sequence (icp_odometry_init) on the same context, a launch before
+ * icp_pmap_odometry_init or while a frame awaits its end, an end with nothing launched, n != H*W (or host memory, timestamps, a
+ * grid sample) for a vertex map, normals_kernel_size not odd in 1..15.
+ * A frame without a single valid target (an all-null vertex map) is no error: as in icp_pmap_register, the residual-norm guard of
+ * the Gauss-Newton step (slam/common/optimization.py:323-327) ends its loop in the first iteration with ICP_OK and the guess
+ * unchanged, and the frame is completed with that pose.  ICP_ERR_INVALID_JACOBIAN needs rows: a few of them, |det H| < 1e-7.
+ * The kind of frame loop is chosen for the life of the context: only icp_destroy ends a kd-tree sequence, so a context that has
+ * seen icp_odometry_init refuses these calls from then on (also one that called it between icp_pmap_odometry_init and frame 0,
+ * while the projective map was still empty), and a context that holds a projective map refuses icp_odometry_init. */
+typedef enum { ICP_FRAME_ROWS = 0, ICP_FRAME_VERTEX_MAP = 1 } icp_frame_layout;
+typedef struct icp_pmap_frame_config {
+    double voxel_size;           /* > 0: GridSample (slam/preprocessing.py:207-226) in front of the frame (rows input only) */
+    float threshold_trans;       /* key-frame test, metres (icp_odometry.py:29-64: 0.1) */
+    float threshold_rot;         /* key-frame test, degrees (0.3) */
+    int32_t constant_velocity;   /* 1: initial guess = the last relative pose (slam/initialization.py:103-119); 0: identity */
+    int32_t targets;             /* rows input — 0: the frame's rows; 1: the pixels of its vertex map.  Vertex-map input: always
+                                    its pixels */
+    int32_t normals_kernel_size; /* compute_normal_map's window (ProjectiveLocalMapConfig, local_map.py:91-111): odd, 1..15;
+                                    default 5 */
+    int32_t copy_cloud;          /* 1: icp_pmap_frame_end will be asked for odometry_pc in host memory: its copy starts in
+                                    icp_pmap_frame_launch, beside the registration */
+} icp_pmap_frame_config;
+void icp_default_pmap_frame_config(icp_pmap_frame_config* cfg);
+int icp_pmap_register_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16]);
+int icp_pmap_odometry_init(icp_ctx* ctx, const icp_pmap_frame_config* cfg);
+int icp_pmap_frame_launch(icp_ctx* ctx, const float* data, int64_t n, int mem, int layout, const double* timestamps,
+                          const float init_pose[16]);
+int icp_pmap_frame_end(icp_ctx* ctx, icp_frame_result* result, float* odometry_pc_out, int64_t cap, int64_t* rows_out,
+                       int out_mem, double* loss_per_iter_out, float* dx_per_iter_out);
+
+/* ---- ... for B sequences per call ------------------------------------------------------------------------------------------
+ * icp_pmap_frame_launch / icp_pmap_frame_end for the members of a batch, as icp_batch_frame_launch / icp_batch_frame_end are
+ * for the kd-tree style map: the projective frame loop (icp_odometry.py:157-246, :360-380; local_map.py:113-235) of B drives
+ * behind two calls.  Per member the calls give what the single calls give on that member's context alone with the same frames,
+ * bit for bit: pose, parameters, iteration count, losses, steps, key-frame decision, samples, odometry_pc, window, model and
+ * every later frame.  One small kernel of its own (the transposition of B vertex maps in one launch).
+ *   icp_batch_pmap_odometry_init  icp_pmap_odometry_init(member, cfg) on every member, every member checked before any is
+ *                      restarted.  The sequence state is the MEMBER's: a member may be stepped by the batch, then alone with
+ *                      icp_pmap_frame_launch / icp_pmap_frame_end, then by the batch again.
+ *   icp_batch_pmap_frame_launch  frames[b] = member b's next frame, icp_batch_frame as for icp_batch_frame_launch (`xyz`: the
+ *                      rows, or the [3,H,W] vertex map with n = H*W); `mem` and `layout` hold for the whole step.  skip != 0:
+ *                      the member sits the step out.  FIRST FRAME (frame index 0): member by member what
+ *                      icp_pmap_frame_launch does for frame 0.  REGISTERING (frame index >= 1), ONE call per stage for the whole
+ *                      group: the uploads from host arrays (ONE pinned arena, ONE upload stream, two device arenas — those of
+ *                      icp_batch_frame_launch), icp_batch_preprocess for a step that grid-samples (rows), icp_batch_project_rows
+ *                      (rows; behind the registration for targets = 0) or ONE transposing launch (vertex maps),
+ *                      icp_batch_stage, the copies of the staged rows and sample counts on ONE copy stream, and
+ *                      icp_batch_pmap_register_launch with every member's guess.
+ *   icp_batch_pmap_frame_end  icp_batch_register_end for the registering group, each member's key-frame test, then ONE
+ *                      icp_batch_pmap_update over the members whose registration succeeded: the key-frame members pass their
+ *                      vertex map, the others NULL.  results, histories, odometry_pc_out / cap / rows_out as for
+ *                      icp_batch_frame_end; a skipped member's result is zeroed with frame_index = -1.
+ * A FAILED REGISTRATION (ICP_ERR_INVALID_JACOBIAN) leaves its member as icp_pmap_frame_end leaves a single context; every other
+ * member completes its frame; the call returns the first such status.  REFUSALS, checked for every member before any member
+ * changes (ICP_ERR_INVALID_ARGUMENT, icp_batch_last_error names the member and the reason, "(nothing was changed)"): a
+ * non-skipped member without a projective sequence, with a kd-tree sequence, point-to-point, an exchange or profiling, in or
+ * awaiting a registration or a frame of its own; a launch while a launch awaits its end; an end with nothing launched; every
+ * member skipped; members that differ in voxel_size, targets, normals_kernel_size, image size or stream; for vertex maps
+ * n != H*W, host memory, timestamps or a grid sample.  Partial steps run on the inner batches of icp_batch_frame_launch (an LRU
+ * of 8 member masks).  A frame the batch has launched is ended by the batch. */
+int icp_batch_pmap_odometry_init(icp_batch* batch, const icp_pmap_frame_config* cfg);
+int icp_batch_pmap_frame_launch(icp_batch* batch, const icp_batch_frame* frames, int mem, int layout);
+int icp_batch_pmap_frame_end(icp_batch* batch, icp_frame_result* results, float* const* odometry_pc_out, const int64_t* cap,
+                             int64_t* rows_out, int out_mem, double* loss_per_iter_out, float* dx_per_iter_out);
+
 /* ---- multi-GPU exchange inside the library ("one-shot P2P write+flag all-reduce") -----------------
  * The per-iteration exchange of the scan-sharded registration without leaving the library: after these three calls
  * icp_register / icp_register_launch on every rank enqueue, per ICP iteration, the iteration kernel and ONE kernel that

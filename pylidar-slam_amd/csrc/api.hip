@@ -328,6 +328,7 @@ void icp_destroy(icp_ctx* ctx) {
     registering_leave(ctx);
     (void)hipDeviceSynchronize();
     frame_loop_release(ctx);
+    pmap_frame_loop_release(ctx);
     DeviceBuffer* bufs[] = {&ctx->map_xyz[0], &ctx->map_xyz[1], &ctx->table,   &ctx->sorted_pts, &ctx->normals,
                             &ctx->nflag,      &ctx->slot_of,    &ctx->rank_of, &ctx->scan_tmp,   &ctx->worklist,
                             &ctx->targets,    &ctx->nn_pos,     &ctx->partials, &ctx->state,
@@ -1973,6 +1974,44 @@ int icp_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_
     if (rc) return rc;
     if ((rc = enqueue_iterations(ctx, true))) return rc;
     return icp_register_end(ctx, result, loss_per_iter_out, dx_per_iter_out);
+}
+
+// icp_pmap_register, enqueued: begin + every iteration on the stream, the result block delivered to its pinned slot behind the
+// last one, collected by icp_register_end.  The kernels of an iteration behind the stop return at once (RegState.done): no host
+// poll decides anything, and the iterations that run are those of icp_pmap_register — the same bits.
+int icp_pmap_register_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16]) {
+    DeviceGuard device_guard(ctx);
+    if (!ctx || n < 0 || (n > 0 && !xyz)) return ICP_ERR_INVALID_ARGUMENT;
+    if (ctx->in_registration || ctx->result_pending())
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_pmap_register_launch: a registration of this context is in progress or "
+                                                   "awaits icp_register_end");
+    int rc = continue_launch(ctx, -1);  // (refuses a context whose batch still holds iterations back)
+    if (rc) return rc;
+    if (ctx->pm_slots.empty()) return fail(ctx, ICP_ERR_EMPTY_MAP, "the local map is empty");
+    if ((rc = ensure_state(ctx))) return rc;
+    const void* in;
+    if ((rc = import_buffer(ctx, xyz, (size_t)n * 12, mem, ctx->targets, &in))) return rc;
+    ctx->tgt_ptr = (const float*)in;
+    ctx->tgt_n = n;
+    ctx->tgt_mode = target_mode;
+    if ((rc = prepare_targets_and_state(ctx, n, init_pose))) return rc;
+    ctx->have_device_pose = false; ctx->device_pose_epoch += 1;  // (as icp_pmap_register)
+    ctx->pm_have_pose = true;
+    ctx->in_registration = true;
+    const int iters = ctx->cfg.max_num_alignments;
+    rc = result_fold_begin(ctx, false);  // (the last solving launch delivers the result block itself)
+    for (int it = 0; !rc && it < iters; ++it) {
+        int blocks = 0;
+        rc = pmap_iterate(ctx, &blocks);
+        if (!rc) rc = launch_sum_solve(ctx, blocks, 1, nullptr, false, it + 1 == iters);
+    }
+    ctx->launch_enqueued = iters;
+    ctx->launch_remaining = 0;
+    if (!rc) rc = enqueue_result_copy(ctx);
+    ctx->result_fold_to = nullptr;
+    ctx->result_folded = false;
+    ctx->in_registration = false;  // the result waits in its slot
+    return rc;
 }
 
 // ---- B sequences per launch (include/icp_mi355x.h: icp_batch_*) ----------------------------------------------------------

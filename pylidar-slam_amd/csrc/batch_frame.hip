@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <map>
 
+#include "batch_frame_loop.h"
 #include "batch_frame_plan.h"
 #include "frame_keyframe.h"
 #include "frame_loop.h"
@@ -19,50 +20,9 @@ using namespace icp;
 
 static_assert(BATCH_FRAME_MAX_MEMBERS == ICP_BATCH_MAX_SEQUENCES, "batch_frame_plan.h sizes its lists for ICP_BATCH_MAX_SEQUENCES members");
 
-struct icp_batch_frames {
-    // member mask -> a batch over those members (the full mask: the batch itself).  Bounded: a serving loop whose drives end,
-    // start and fail in arbitrary slots meets ever new masks, and every inner batch owns pinned descriptor slots, device tables
-    // and events — beyond INNER_MAX of them the least recently used one is destroyed (one device synchronisation; a mask that
-    // comes back is created again)
-    static constexpr size_t INNER_MAX = 8;
-    struct Inner {
-        icp_batch* batch;
-        uint64_t used;
-    };
-    std::map<uint32_t, Inner> inner;
-    uint64_t tick = 0;
-    // ---- the step between icp_batch_frame_launch and icp_batch_frame_end
-    bool pending = false;
-    BatchFramePlan plan;
-    int mem = ICP_MEM_DEVICE;
-    int64_t n[ICP_BATCH_MAX_SEQUENCES] = {};
-    bool sampled[ICP_BATCH_MAX_SEQUENCES] = {};
-    bool copied[ICP_BATCH_MAX_SEQUENCES] = {};     // the member's staged rows are on their way to pin_out
-    size_t out_offset[ICP_BATCH_MAX_SEQUENCES] = {};  // ... at this offset
-    bool copy_started = false;
-    // ---- input: ONE pinned arena -> one of two device arenas, on ONE upload stream, whatever the member count
-    void* pin_in = nullptr;
-    size_t pin_in_bytes = 0;
-    hipEvent_t pin_in_free = nullptr;
-    bool pin_in_busy = false;
-    DeviceBuffer arena[2];
-    hipEvent_t arena_read[2] = {nullptr, nullptr};  // the step that read the arena last has been enqueued up to here
-    bool arena_used[2] = {false, false};
-    int which = 0;
-    hipStream_t upload_stream = nullptr;
-    // ---- odometry_pc and the sample counts: ONE copy stream, ONE pinned arena (the counts lead it)
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t copy_done = nullptr;
-    void* pin_out = nullptr;
-    size_t pin_out_bytes = 0;
-    int* pin_counts = nullptr;  // [ICP_BATCH_MAX_SEQUENCES]
-};
+namespace icp {
 
-namespace {
-
-constexpr size_t ALIGN = 256;
-inline size_t align_up(size_t v) { return (v + ALIGN - 1) & ~(ALIGN - 1); }
-
+// ---- shared with the projective form (batch_pmap_frame.hip): batch_frame_loop.h
 int bf_fail(icp_batch* b, int code, const std::string& msg) {
     b->error = msg;
     return code;
@@ -72,12 +32,6 @@ int bf_hip(icp_batch* b, hipError_t e, const char* what) {
     if (e == hipSuccess) return ICP_OK;
     return bf_fail(b, ICP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-#define BF_HIP(b, expr)                               \
-    do {                                              \
-        const int _rc = bf_hip((b), (expr), #expr);   \
-        if (_rc) return _rc;                          \
-    } while (0)
-
 int bf_member_fail(icp_batch* b, int rc, const char* who, int member) {
     return bf_fail(b, rc, std::string(who) + ", member " + std::to_string(member) + ": " + b->members[member]->error);
 }
@@ -137,33 +91,6 @@ int inner_fail(icp_batch* b, icp_batch* inner, int rc) {
     return rc;
 }
 
-void fill_members(icp_batch* b, const icp_batch_frame* frames, BatchFrameMember* out) {
-    for (size_t i = 0; i < b->members.size(); ++i) {
-        const icp_ctx* ctx = b->members[i];
-        const icp_frame_loop* f = ctx->frame;
-        BatchFrameMember& m = out[i];
-        memset(&m, 0, sizeof(m));
-        m.skip = frames[i].skip != 0;
-        m.has_sequence = f != nullptr;
-        m.frame_index = f ? f->index : 0;
-        m.voxel_size = f ? f->cfg.voxel_size : 0.0;
-        m.targets = f ? f->cfg.targets : 0;
-        m.point_to_point = ctx->cost != ICP_COST_POINT_TO_PLANE;
-        m.projective_map = !ctx->pm_slots.empty();
-        m.exchange = ctx->exchange_on;
-        m.profiling = ctx->prof.enabled != 0;
-        m.registering = ctx->in_registration || ctx->result_pending() || ctx->batch_hold;
-        m.frame_launched = f && f->launched;
-        m.stream = (uint64_t)(uintptr_t)ctx->stream;
-    }
-}
-
-int refuse(icp_batch* b, const char* who, const BatchFramePlan& plan) {
-    std::string msg = std::string(who);
-    if (plan.refused_member >= 0) msg += ", member " + std::to_string(plan.refused_member);
-    return bf_fail(b, ICP_ERR_INVALID_ARGUMENT, msg + ": " + plan.reason + " (nothing was changed)");
-}
-
 // host rows (and timestamps) of the members in `who` -> the pinned arena -> the next device arena, ONE copy on the upload
 // stream; the batch's stream waits for it.  rows[] / ts[] receive the device addresses.
 int upload(icp_batch* b, icp_batch_frames* s, const icp_batch_frame* frames, const int32_t* who, int n_who, hipStream_t stream,
@@ -213,6 +140,162 @@ int upload(icp_batch* b, icp_batch_frames* s, const icp_batch_frame* frames, con
     return ICP_OK;
 }
 
+// de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126) of the registering members `reg` (member
+// indices; ctxs / loops / guess / have_guess / r_rows / r_n by position k, ts by member index): icp_batch_preprocess on `rb` for
+// a step that grid-samples, icp_frame_launch's own two launches for a de-skewed member otherwise.  r_rows[k] becomes what the
+// frame goes on with; s->sampled / s->copied and the loops' frame fields are set.
+int batch_frames_preprocess(icp_batch* b, icp_batch* rb, icp_batch_frames* s, const char* who, const int32_t* reg, int nr,
+                            icp_ctx* const* ctxs, icp_frame_loop* const* loops, double voxel_size, const float* const* guess,
+                            const bool* have_guess, const double* const* ts, const float** r_rows, const int64_t* r_n) {
+    bool skew[ICP_BATCH_MAX_SEQUENCES];
+    const bool sample_step = voxel_size > 0;
+    for (int k = 0; k < nr; ++k) {
+        const int i = reg[k];
+        skew[k] = r_n[k] > 0 && ts[i] != nullptr && have_guess[k];
+        s->sampled[i] = r_n[k] > 0 && sample_step;
+        s->copied[i] = false;
+    }
+    auto member_hip = [&](int k, hipError_t e, const char* what) -> int {
+        if (e == hipSuccess) return ICP_OK;
+        return bf_fail(b, ICP_ERR_HIP, std::string(who) + ", member " + std::to_string(reg[k]) + ": " + what + ": " + hipGetErrorString(e));
+    };
+    int rc = ICP_OK;
+    for (int k = 0; k < nr && !rc; ++k) {
+        icp_frame_loop* f = loops[k];
+        const size_t n = (size_t)r_n[k];
+        if (skew[k]) rc = member_hip(k, f->skew64.reserve(n * 24), "reserve(skew64)");
+        if (!rc && (s->sampled[reg[k]] || skew[k])) rc = member_hip(k, f->samp32.reserve(n * 12), "reserve(samp32)");
+        if (!rc && s->sampled[reg[k]] && skew[k]) rc = member_hip(k, f->samp64.reserve(n * 24), "reserve(samp64)");
+        if (!rc) rc = member_hip(k, f->count.reserve(64), "reserve(count)");
+    }
+    if (rc) return rc;
+    if (sample_step) {
+        icp_preprocess_frame pre[ICP_BATCH_MAX_SEQUENCES];
+        memset(pre, 0, sizeof(pre));
+        for (int k = 0; k < nr; ++k) {
+            icp_frame_loop* f = loops[k];
+            icp_preprocess_frame& p = pre[k];
+            p.xyz = r_rows[k];
+            p.n = r_n[k];
+            p.count_out = f->count.as<int32_t>();
+            if (r_n[k] <= 0) continue;
+            if (skew[k]) {
+                p.timestamps = ts[reg[k]];
+                for (int e = 0; e < 16; ++e) p.rel_pose[e] = (double)guess[k][e];
+                p.distorted_out = f->skew64.as<double>();
+                p.samples_out = f->samp64.as<double>();
+            }
+            p.samples_f32_out = f->samp32.as<float>();
+            r_rows[k] = f->samp32.as<float>();
+        }
+        if ((rc = icp_batch_preprocess(rb, pre, voxel_size))) return inner_fail(b, rb, rc);
+    } else {
+        for (int k = 0; k < nr; ++k) {  // (no grid sample: a de-skewed member takes icp_frame_launch's own two launches)
+            if (!skew[k]) continue;
+            icp_frame_loop* f = loops[k];
+            double rel[16];
+            for (int e = 0; e < 16; ++e) rel[e] = (double)guess[k][e];
+            if ((rc = distort_device(ctxs[k], r_rows[k], ts[reg[k]], r_n[k], rel, f->skew64.as<double>())) ||
+                (rc = rows_to_f32_device(ctxs[k], f->skew64.as<double>(), 3 * r_n[k], f->samp32.as<float>())))
+                return bf_member_fail(b, rc, who, reg[k]);
+            r_rows[k] = f->samp32.as<float>();
+        }
+    }
+    for (int k = 0; k < nr; ++k) {
+        icp_frame_loop* f = loops[k];
+        f->frame_rows = r_rows[k];
+        f->n = r_n[k];
+        f->sampled = s->sampled[reg[k]];
+        f->copy_started = false;
+    }
+    return ICP_OK;
+}
+
+// the copies towards the host, beside the registration: behind the staging, on ONE stream of the batch's own — the staged rows
+// of the members with cloud[k] and the sample counts of the sampled ones, into ONE pinned arena
+int batch_frames_copy_start(icp_batch* b, icp_batch_frames* s, const int32_t* reg, int nr, icp_ctx* const* ctxs,
+                            icp_frame_loop* const* loops, const bool* cloud, const int64_t* r_n) {
+    size_t bytes = 0;
+    bool any = false;
+    for (int k = 0; k < nr; ++k) {
+        const int i = reg[k];
+        s->out_offset[i] = bytes;
+        if (cloud[k] && r_n[k] > 0) {
+            bytes += align_up((size_t)r_n[k] * 12);
+            s->copied[i] = true;
+            any = true;
+        }
+        any = any || s->sampled[i];
+    }
+    if (!any) return ICP_OK;
+    int rc = ICP_OK;
+    if (!s->copy_stream) rc = bf_hip(b, hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking), "hipStreamCreate(copy)");
+    if (!rc && !s->copy_done) rc = bf_hip(b, hipEventCreateWithFlags(&s->copy_done, hipEventDisableTiming), "hipEventCreate(copy)");
+    if (!rc && !s->pin_counts)
+        rc = bf_hip(b, hipHostMalloc((void**)&s->pin_counts, sizeof(int) * ICP_BATCH_MAX_SEQUENCES, hipHostMallocDefault),
+                    "hipHostMalloc(counts)");
+    if (!rc && bytes > 0) rc = pinned_reserve(b, &s->pin_out, &s->pin_out_bytes, bytes);
+    // (the members' staging events are recorded one behind the other on the batch's stream: the last one covers all)
+    if (!rc) rc = bf_hip(b, hipStreamWaitEvent(s->copy_stream, ctxs[nr - 1]->staged_event, 0), "hipStreamWaitEvent(staged)");
+    for (int k = 0; k < nr && !rc; ++k) {
+        const int i = reg[k];
+        if (s->sampled[i])
+            rc = bf_hip(b, hipMemcpyAsync(&s->pin_counts[i], loops[k]->count.ptr, sizeof(int), hipMemcpyDeviceToHost, s->copy_stream),
+                        "hipMemcpyAsync(count)");
+        if (!rc && s->copied[i])
+            rc = bf_hip(b, hipMemcpyAsync((char*)s->pin_out + s->out_offset[i], ctxs[k]->staged_xyz.ptr, (size_t)r_n[k] * 12,
+                                          hipMemcpyDeviceToHost, s->copy_stream),
+                        "hipMemcpyAsync(odometry_pc)");
+    }
+    if (!rc) rc = bf_hip(b, hipEventRecord(s->copy_done, s->copy_stream), "hipEventRecord(copy_done)");
+    if (rc) {
+        if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
+        return rc;
+    }
+    s->copy_started = true;
+    return ICP_OK;
+}
+
+// what reads the device arena of this step's upload is on the stream: the upload of the step after next waits for it
+int batch_frames_arena_read(icp_batch* b, icp_batch_frames* s, hipStream_t stream) {
+    hipEvent_t& e = s->arena_read[s->which];
+    if (!e) BF_HIP(b, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    BF_HIP(b, hipEventRecord(e, stream));
+    s->arena_used[s->which] = true;
+    return ICP_OK;
+}
+
+}  // namespace icp
+
+namespace {
+
+void fill_members(icp_batch* b, const icp_batch_frame* frames, BatchFrameMember* out) {
+    for (size_t i = 0; i < b->members.size(); ++i) {
+        const icp_ctx* ctx = b->members[i];
+        const icp_frame_loop* f = ctx->frame;
+        BatchFrameMember& m = out[i];
+        memset(&m, 0, sizeof(m));
+        m.skip = frames[i].skip != 0;
+        m.has_sequence = f != nullptr;
+        m.frame_index = f ? f->index : 0;
+        m.voxel_size = f ? f->cfg.voxel_size : 0.0;
+        m.targets = f ? f->cfg.targets : 0;
+        m.point_to_point = ctx->cost != ICP_COST_POINT_TO_PLANE;
+        m.projective_map = !ctx->pm_slots.empty();
+        m.exchange = ctx->exchange_on;
+        m.profiling = ctx->prof.enabled != 0;
+        m.registering = ctx->in_registration || ctx->result_pending() || ctx->batch_hold;
+        m.frame_launched = f && f->launched;
+        m.stream = (uint64_t)(uintptr_t)ctx->stream;
+    }
+}
+
+int refuse(icp_batch* b, const char* who, const BatchFramePlan& plan) {
+    std::string msg = std::string(who);
+    if (plan.refused_member >= 0) msg += ", member " + std::to_string(plan.refused_member);
+    return bf_fail(b, ICP_ERR_INVALID_ARGUMENT, msg + ": " + plan.reason + " (nothing was changed)");
+}
+
 // a step launched and never ended: its registrations are collected and dropped, its copies waited for
 void drop_pending(icp_batch* b, icp_batch_frames* s) {
     if (!s->pending) return;
@@ -248,6 +331,7 @@ void batch_frames_release(icp_batch* b) {
     icp_batch_frames* s = b ? b->frames : nullptr;
     if (!s) return;
     drop_pending(b, s);
+    batch_pmap_drop_pending(b);
     (void)hipDeviceSynchronize();
     for (auto& kv : s->inner) icp_batch_destroy(kv.second.batch);
     s->arena[0].release();
@@ -354,9 +438,8 @@ int icp_batch_frame_launch(icp_batch* b, const icp_batch_frame* frames, int mem)
         const float* r_rows[ICP_BATCH_MAX_SEQUENCES];
         int64_t r_n[ICP_BATCH_MAX_SEQUENCES];
         const float* guess[ICP_BATCH_MAX_SEQUENCES];
-        bool have_guess[ICP_BATCH_MAX_SEQUENCES], skew[ICP_BATCH_MAX_SEQUENCES];
+        bool have_guess[ICP_BATCH_MAX_SEQUENCES];
         const icp_frame_config& c0 = b->members[plan.registering[0]]->frame->cfg;
-        const bool sample_step = c0.voxel_size > 0;
         for (int k = 0; k < nr; ++k) {
             const int i = plan.registering[k];
             ctxs[k] = b->members[i];
@@ -367,9 +450,6 @@ int icp_batch_frame_launch(icp_batch* b, const icp_batch_frame* frames, int mem)
             // the initial guess (ConstantVelocityInitialization, slam/initialization.py:103-119): icp_frame_launch's rule
             have_guess[k] = fr.init_pose != nullptr || loops[k]->cfg.constant_velocity != 0;
             guess[k] = fr.init_pose ? fr.init_pose : loops[k]->last_pose;
-            skew[k] = fr.n > 0 && ts[i] != nullptr && have_guess[k];
-            s->sampled[i] = fr.n > 0 && sample_step;
-            s->copied[i] = false;
         }
         auto member_hip = [&](int k, hipError_t e, const char* what) -> int {
             if (e == hipSuccess) return ICP_OK;
@@ -377,62 +457,10 @@ int icp_batch_frame_launch(icp_batch* b, const icp_batch_frame* frames, int mem)
                                                what + ": " + hipGetErrorString(e));
         };
         // ---- de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126)
-        rc = ICP_OK;
-        for (int k = 0; k < nr && !rc; ++k) {
-            icp_frame_loop* f = loops[k];
-            const size_t n = (size_t)r_n[k];
-            if (skew[k]) rc = member_hip(k, f->skew64.reserve(n * 24), "reserve(skew64)");
-            if (!rc && (s->sampled[plan.registering[k]] || skew[k])) rc = member_hip(k, f->samp32.reserve(n * 12), "reserve(samp32)");
-            if (!rc && s->sampled[plan.registering[k]] && skew[k]) rc = member_hip(k, f->samp64.reserve(n * 24), "reserve(samp64)");
-            if (!rc) rc = member_hip(k, f->count.reserve(64), "reserve(count)");
-        }
-        if (rc) {
+        if ((rc = batch_frames_preprocess(b, rb, s, "icp_batch_frame_launch", plan.registering, nr, ctxs, loops, c0.voxel_size, guess,
+                                          have_guess, ts, r_rows, r_n))) {
             end_first();
             return rc;
-        }
-        if (sample_step) {
-            icp_preprocess_frame pre[ICP_BATCH_MAX_SEQUENCES];
-            memset(pre, 0, sizeof(pre));
-            for (int k = 0; k < nr; ++k) {
-                icp_frame_loop* f = loops[k];
-                icp_preprocess_frame& p = pre[k];
-                p.xyz = r_rows[k];
-                p.n = r_n[k];
-                p.count_out = f->count.as<int32_t>();
-                if (r_n[k] <= 0) continue;
-                if (skew[k]) {
-                    p.timestamps = ts[plan.registering[k]];
-                    for (int e = 0; e < 16; ++e) p.rel_pose[e] = (double)guess[k][e];
-                    p.distorted_out = f->skew64.as<double>();
-                    p.samples_out = f->samp64.as<double>();
-                }
-                p.samples_f32_out = f->samp32.as<float>();
-                r_rows[k] = f->samp32.as<float>();
-            }
-            if ((rc = icp_batch_preprocess(rb, pre, c0.voxel_size))) {
-                end_first();
-                return inner_fail(b, rb, rc);
-            }
-        } else {
-            for (int k = 0; k < nr; ++k) {  // (no grid sample: a de-skewed member takes icp_frame_launch's own two launches)
-                if (!skew[k]) continue;
-                icp_frame_loop* f = loops[k];
-                double rel[16];
-                for (int e = 0; e < 16; ++e) rel[e] = (double)guess[k][e];
-                if ((rc = distort_device(ctxs[k], r_rows[k], ts[plan.registering[k]], r_n[k], rel, f->skew64.as<double>())) ||
-                    (rc = rows_to_f32_device(ctxs[k], f->skew64.as<double>(), 3 * r_n[k], f->samp32.as<float>()))) {
-                    end_first();
-                    return bf_member_fail(b, rc, "icp_batch_frame_launch", plan.registering[k]);
-                }
-                r_rows[k] = f->samp32.as<float>();
-            }
-        }
-        for (int k = 0; k < nr; ++k) {
-            icp_frame_loop* f = loops[k];
-            f->frame_rows = r_rows[k];
-            f->n = r_n[k];
-            f->sampled = s->sampled[plan.registering[k]];
-            f->copy_started = false;
         }
         // ---- projection (targets = 1), staging, copy-out, registration — the plugin's order
         const float* targets[ICP_BATCH_MAX_SEQUENCES];
@@ -473,45 +501,11 @@ int icp_batch_frame_launch(icp_batch* b, const icp_batch_frame* frames, int mem)
         for (int k = 0; k < nr; ++k) loops[k]->staged = true;
         // ---- the copies towards the host, beside the registration: behind the staging, on ONE stream of the batch's own
         {
-            size_t bytes = 0;
-            bool any = false;
-            for (int k = 0; k < nr; ++k) {
-                const int i = plan.registering[k];
-                s->out_offset[i] = bytes;
-                if (loops[k]->cfg.copy_cloud && r_n[k] > 0) {
-                    bytes += align_up((size_t)r_n[k] * 12);
-                    s->copied[i] = true;
-                    any = true;
-                }
-                any = any || s->sampled[i];
-            }
-            if (any) {
-                rc = ICP_OK;
-                if (!s->copy_stream) rc = bf_hip(b, hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking), "hipStreamCreate(copy)");
-                if (!rc && !s->copy_done) rc = bf_hip(b, hipEventCreateWithFlags(&s->copy_done, hipEventDisableTiming), "hipEventCreate(copy)");
-                if (!rc && !s->pin_counts)
-                    rc = bf_hip(b, hipHostMalloc((void**)&s->pin_counts, sizeof(int) * ICP_BATCH_MAX_SEQUENCES, hipHostMallocDefault),
-                                "hipHostMalloc(counts)");
-                if (!rc && bytes > 0) rc = pinned_reserve(b, &s->pin_out, &s->pin_out_bytes, bytes);
-                // (the members' staging events are recorded one behind the other on the batch's stream: the last one covers all)
-                if (!rc) rc = bf_hip(b, hipStreamWaitEvent(s->copy_stream, ctxs[nr - 1]->staged_event, 0), "hipStreamWaitEvent(staged)");
-                for (int k = 0; k < nr && !rc; ++k) {
-                    const int i = plan.registering[k];
-                    if (s->sampled[i])
-                        rc = bf_hip(b, hipMemcpyAsync(&s->pin_counts[i], loops[k]->count.ptr, sizeof(int), hipMemcpyDeviceToHost, s->copy_stream),
-                                    "hipMemcpyAsync(count)");
-                    if (!rc && s->copied[i])
-                        rc = bf_hip(b, hipMemcpyAsync((char*)s->pin_out + s->out_offset[i], ctxs[k]->staged_xyz.ptr, (size_t)r_n[k] * 12,
-                                                      hipMemcpyDeviceToHost, s->copy_stream),
-                                    "hipMemcpyAsync(odometry_pc)");
-                }
-                if (!rc) rc = bf_hip(b, hipEventRecord(s->copy_done, s->copy_stream), "hipEventRecord(copy_done)");
-                if (rc) {
-                    if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
-                    end_first();
-                    return rc;
-                }
-                s->copy_started = true;
+            bool cloud[ICP_BATCH_MAX_SEQUENCES];
+            for (int k = 0; k < nr; ++k) cloud[k] = loops[k]->cfg.copy_cloud != 0;
+            if ((rc = batch_frames_copy_start(b, s, plan.registering, nr, ctxs, loops, cloud, r_n))) {
+                end_first();
+                return rc;
             }
         }
         // ---- the registration: from the device-resident poses when every member would do so on its own, the host guesses otherwise
@@ -540,12 +534,7 @@ int icp_batch_frame_launch(icp_batch* b, const icp_batch_frame* frames, int mem)
         }
     }
     for (int k = 0; k < plan.n_first; ++k) b->members[plan.first[k]]->frame->batched = true;
-    if (uploaded) {  // what reads the device arena is on the stream: the upload of the step after next waits for it
-        hipEvent_t& e = s->arena_read[s->which];
-        if (!e) BF_HIP(b, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        BF_HIP(b, hipEventRecord(e, stream));
-        s->arena_used[s->which] = true;
-    }
+    if (uploaded && (rc = batch_frames_arena_read(b, s, stream))) return rc;
     s->plan = plan;
     s->pending = true;
     return ICP_OK;

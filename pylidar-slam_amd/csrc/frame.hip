@@ -24,6 +24,23 @@ int frame_refusals(icp_ctx* ctx, const char* who) {
     return ICP_OK;
 }
 
+// a frame launched and never ended: its registration is collected and dropped, its copy waited for
+void frame_drop_pending(icp_ctx* ctx, icp_frame_loop* f) {
+    if (!f->launched) return;
+    if (f->registered && ctx->result_pending()) {
+        icp_register_result r;
+        (void)icp_register_end(ctx, &r, nullptr, nullptr);
+    }
+    if (f->copy_started) (void)hipEventSynchronize(f->copy_done);
+    f->copy_started = false;
+    f->launched = f->registered = false;
+}
+
+}  // namespace
+
+namespace icp {
+
+// ---- shared with the projective frame calls (pmap_frame.hip): frame_loop.h
 int pinned_reserve(icp_ctx* ctx, void** ptr, size_t* have, size_t need) {
     if (*ptr && *have >= need) return ICP_OK;
     if (*ptr) ICP_HIP(ctx, hipHostFree(*ptr));
@@ -66,21 +83,71 @@ int frame_upload(icp_ctx* ctx, icp_frame_loop* f, const float* xyz, const double
     return ICP_OK;
 }
 
-// a frame launched and never ended: its registration is collected and dropped, its copy waited for
-void frame_drop_pending(icp_ctx* ctx, icp_frame_loop* f) {
-    if (!f->launched) return;
-    if (f->registered && ctx->result_pending()) {
-        icp_register_result r;
-        (void)icp_register_end(ctx, &r, nullptr, nullptr);
+// de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126) of device rows, into the loop's
+// buffers; guess = NULL: no de-skew.  *rows_out: the rows the frame goes on with (the input itself when nothing applies)
+int frame_preprocess_device(icp_ctx* ctx, icp_frame_loop* f, double voxel_size, const float* rows, int64_t n, const double* ts,
+                            const float* guess, const float** rows_out, bool* sampled_out) {
+    int rc;
+    const bool skew = n > 0 && ts != nullptr && guess != nullptr;
+    const bool sample = n > 0 && voxel_size > 0;
+    if (skew) {
+        double rel[16];
+        for (int i = 0; i < 16; ++i) rel[i] = (double)guess[i];
+        ICP_HIP(ctx, f->skew64.reserve((size_t)n * 24));
+        if ((rc = distort_device(ctx, rows, ts, n, rel, f->skew64.as<double>()))) return rc;
     }
-    if (f->copy_started) (void)hipEventSynchronize(f->copy_done);
-    f->copy_started = false;
-    f->launched = f->registered = false;
+    if (sample || skew) ICP_HIP(ctx, f->samp32.reserve((size_t)n * 12));
+    ICP_HIP(ctx, f->count.reserve(64));
+    if (sample && skew) {
+        ICP_HIP(ctx, f->samp64.reserve((size_t)n * 24));
+        if ((rc = icp_grid_sample_padded_f64(ctx, f->skew64.as<double>(), n, voxel_size, nullptr, f->samp64.as<double>(),
+                                             f->count.as<int32_t>())))
+            return rc;
+        if ((rc = rows_to_f32_device(ctx, f->samp64.as<double>(), 3 * n, f->samp32.as<float>()))) return rc;
+        rows = f->samp32.as<float>();
+    } else if (sample) {
+        if ((rc = icp_grid_sample_padded(ctx, rows, n, voxel_size, nullptr, f->samp32.as<float>(), f->count.as<int32_t>())))
+            return rc;
+        rows = f->samp32.as<float>();
+    } else if (skew) {
+        if ((rc = rows_to_f32_device(ctx, f->skew64.as<double>(), 3 * n, f->samp32.as<float>()))) return rc;
+        rows = f->samp32.as<float>();
+    }
+    *rows_out = rows;
+    *sampled_out = sample;
+    return ICP_OK;
 }
 
-}  // namespace
+// the staged rows (and the grid sample's count) towards pinned memory, beside the registration: behind the staging (its
+// event), on a stream of the loop's own
+int frame_copy_start(icp_ctx* ctx, icp_frame_loop* f, bool sample, bool cloud, int64_t n) {
+    int rc;
+    if (!f->copy_stream) ICP_HIP(ctx, hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking));
+    if (!f->copy_done) ICP_HIP(ctx, hipEventCreateWithFlags(&f->copy_done, hipEventDisableTiming));
+    if (!f->pin_count) ICP_HIP(ctx, hipHostMalloc((void**)&f->pin_count, sizeof(int), hipHostMallocDefault));
+    ICP_HIP(ctx, hipStreamWaitEvent(f->copy_stream, ctx->staged_event, 0));
+    if (sample)
+        ICP_HIP(ctx, hipMemcpyAsync(f->pin_count, f->count.ptr, sizeof(int), hipMemcpyDeviceToHost, f->copy_stream));
+    if (cloud) {
+        if ((rc = pinned_reserve(ctx, &f->pin_out, &f->pin_out_bytes, (size_t)n * 12))) return rc;
+        ICP_HIP(ctx, hipMemcpyAsync(f->pin_out, ctx->staged_xyz.ptr, (size_t)n * 12, hipMemcpyDeviceToHost, f->copy_stream));
+    }
+    ICP_HIP(ctx, hipEventRecord(f->copy_done, f->copy_stream));
+    f->copy_started = true;
+    return ICP_OK;
+}
 
-namespace icp {
+void frame_buffers_release(icp_frame_loop* f) {
+    DeviceBuffer* bufs[] = {&f->slot[0], &f->slot[1], &f->skew64, &f->samp64, &f->samp32, &f->vmap, &f->rows, &f->count};
+    for (DeviceBuffer* b : bufs) b->release();
+    if (f->pin_in) (void)hipHostFree(f->pin_in);
+    if (f->pin_out) (void)hipHostFree(f->pin_out);
+    if (f->pin_count) (void)hipHostFree(f->pin_count);
+    if (f->pin_in_free) (void)hipEventDestroy(f->pin_in_free);
+    if (f->copy_done) (void)hipEventDestroy(f->copy_done);
+    if (f->upload_stream) (void)hipStreamDestroy(f->upload_stream);
+    if (f->copy_stream) (void)hipStreamDestroy(f->copy_stream);
+}
 
 // what icp_odometry_init refuses, nothing changed (icp_batch_odometry_init asks every member first; own_batch: the frame a
 // batch has launched on the context is that batch's own step, which it drops itself)
@@ -97,15 +164,7 @@ int frame_init_check(icp_ctx* ctx, const icp_frame_config* cfg, bool own_batch) 
 void frame_loop_release(icp_ctx* ctx) {
     icp_frame_loop* f = ctx ? ctx->frame : nullptr;
     if (!f) return;
-    DeviceBuffer* bufs[] = {&f->slot[0], &f->slot[1], &f->skew64, &f->samp64, &f->samp32, &f->vmap, &f->rows, &f->count};
-    for (DeviceBuffer* b : bufs) b->release();
-    if (f->pin_in) (void)hipHostFree(f->pin_in);
-    if (f->pin_out) (void)hipHostFree(f->pin_out);
-    if (f->pin_count) (void)hipHostFree(f->pin_count);
-    if (f->pin_in_free) (void)hipEventDestroy(f->pin_in_free);
-    if (f->copy_done) (void)hipEventDestroy(f->copy_done);
-    if (f->upload_stream) (void)hipStreamDestroy(f->upload_stream);
-    if (f->copy_stream) (void)hipStreamDestroy(f->copy_stream);
+    frame_buffers_release(f);
     delete f;
     ctx->frame = nullptr;
 }
@@ -177,31 +236,8 @@ int frame_launch_device(icp_ctx* ctx, const float* rows, int64_t n, const double
     const bool have_guess = init_pose != nullptr || c.constant_velocity != 0;
     const float* guess = init_pose ? init_pose : f->last_pose;  // (identity without constant_velocity: see below)
     // ---- de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126)
-    const bool skew = n > 0 && ts != nullptr && have_guess;
-    const bool sample = n > 0 && c.voxel_size > 0;
-    if (skew) {
-        double rel[16];
-        for (int i = 0; i < 16; ++i) rel[i] = (double)guess[i];
-        ICP_HIP(ctx, f->skew64.reserve((size_t)n * 24));
-        if ((rc = distort_device(ctx, rows, ts, n, rel, f->skew64.as<double>()))) return rc;
-    }
-    if (sample || skew) ICP_HIP(ctx, f->samp32.reserve((size_t)n * 12));
-    ICP_HIP(ctx, f->count.reserve(64));
-    if (sample && skew) {
-        ICP_HIP(ctx, f->samp64.reserve((size_t)n * 24));
-        if ((rc = icp_grid_sample_padded_f64(ctx, f->skew64.as<double>(), n, c.voxel_size, nullptr, f->samp64.as<double>(),
-                                             f->count.as<int32_t>())))
-            return rc;
-        if ((rc = rows_to_f32_device(ctx, f->samp64.as<double>(), 3 * n, f->samp32.as<float>()))) return rc;
-        rows = f->samp32.as<float>();
-    } else if (sample) {
-        if ((rc = icp_grid_sample_padded(ctx, rows, n, c.voxel_size, nullptr, f->samp32.as<float>(), f->count.as<int32_t>())))
-            return rc;
-        rows = f->samp32.as<float>();
-    } else if (skew) {
-        if ((rc = rows_to_f32_device(ctx, f->skew64.as<double>(), 3 * n, f->samp32.as<float>()))) return rc;
-        rows = f->samp32.as<float>();
-    }
+    bool sample = false;
+    if ((rc = frame_preprocess_device(ctx, f, c.voxel_size, rows, n, ts, have_guess ? guess : nullptr, &rows, &sample))) return rc;
     f->frame_rows = rows;
     f->n = n;
     f->sampled = sample;
@@ -246,19 +282,7 @@ int frame_launch_device(icp_ctx* ctx, const float* rows, int64_t n, const double
     f->staged = sample || c.stage_max_rows <= 0 || n <= (int64_t)c.stage_max_rows || c.copy_cloud != 0;
     if (f->staged && (rc = icp_map_stage_cloud(ctx, rows, n, ICP_MEM_DEVICE, ICP_TARGETS_ALL))) return rc;
     if (f->staged && (sample || (c.copy_cloud && n > 0))) {
-        // beside the registration: behind the staging (its event), on a stream of the context's own
-        if (!f->copy_stream) ICP_HIP(ctx, hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking));
-        if (!f->copy_done) ICP_HIP(ctx, hipEventCreateWithFlags(&f->copy_done, hipEventDisableTiming));
-        if (!f->pin_count) ICP_HIP(ctx, hipHostMalloc((void**)&f->pin_count, sizeof(int), hipHostMallocDefault));
-        ICP_HIP(ctx, hipStreamWaitEvent(f->copy_stream, ctx->staged_event, 0));
-        if (sample)
-            ICP_HIP(ctx, hipMemcpyAsync(f->pin_count, f->count.ptr, sizeof(int), hipMemcpyDeviceToHost, f->copy_stream));
-        if (c.copy_cloud && n > 0) {
-            if ((rc = pinned_reserve(ctx, &f->pin_out, &f->pin_out_bytes, (size_t)n * 12))) return rc;
-            ICP_HIP(ctx, hipMemcpyAsync(f->pin_out, ctx->staged_xyz.ptr, (size_t)n * 12, hipMemcpyDeviceToHost, f->copy_stream));
-        }
-        ICP_HIP(ctx, hipEventRecord(f->copy_done, f->copy_stream));
-        f->copy_started = true;
+        if ((rc = frame_copy_start(ctx, f, sample, c.copy_cloud && n > 0, n))) return rc;
     }
     const bool from_last = c.constant_velocity != 0 && !init_pose && f->index >= 2 && ctx->have_device_pose &&
                            f->pose_epoch == ctx->device_pose_epoch;

@@ -37,7 +37,40 @@ struct icp_frame_loop {
     bool copy_started = false;
 };
 
+// The sequence state behind icp_pmap_odometry_init / icp_pmap_frame_launch / icp_pmap_frame_end (pmap_frame.hip): the frame
+// loop against the projective local map.  `io` lends the upload slots, the preprocessing buffers and the copy-out stream of the
+// kd-tree loop (its sequence fields stay unused): the helpers below serve both loops.
+struct icp_pmap_frame_loop {
+    icp_pmap_frame_config cfg;
+    icp_frame_loop io;
+    int32_t index = 0;        // frames completed since icp_pmap_odometry_init
+    bool launched = false;    // a frame awaits its icp_pmap_frame_end
+    bool registered = false;  // ... with a registration enqueued (false: frame 0)
+    bool batched = false;     // ... launched by icp_batch_pmap_frame_launch: icp_batch_pmap_frame_end ends it
+    float delta[16];          // `_delta_since_map_update`
+    float last_pose[16];      // the last relative pose (the constant-velocity guess)
+    const float* frame_vmap = nullptr;  // [3,H,W] on the device: what a key frame inserts (the input itself, or io.vmap)
+    int64_t n = 0;            // rows handed in (vertex-map input: H*W)
+    bool sampled = false;
+    const float* valid_rows = nullptr;  // [n,3] on the device: the rows odometry_pc is compacted from ...
+    int valid_mode = 0;       // ... with this icp_target_mode (vertex-map input: null pixels dropped as well)
+    bool staged = false;      // ... compacted and counted in front of the registration (icp_map_stage_cloud)
+};
+
 namespace icp {
+// ---- shared by the two loops (frame.hip)
+int pinned_reserve(icp_ctx* ctx, void** ptr, size_t* have, size_t need);
+// host rows (and timestamps) -> pinned buffer -> the next of two device slots, on the loop's upload stream
+int frame_upload(icp_ctx* ctx, icp_frame_loop* f, const float* xyz, const double* ts, int64_t n, const float** rows_out,
+                 const double** ts_out);
+// de-skew (guess != NULL and ts != NULL) -> padded grid sample (voxel_size > 0) -> float32, into the loop's buffers
+int frame_preprocess_device(icp_ctx* ctx, icp_frame_loop* f, double voxel_size, const float* rows, int64_t n, const double* ts,
+                            const float* guess, const float** rows_out, bool* sampled_out);
+// the staged rows (cloud) and the grid sample's count (sample) towards pinned memory, beside the registration
+int frame_copy_start(icp_ctx* ctx, icp_frame_loop* f, bool sample, bool cloud, int64_t n);
+void frame_buffers_release(icp_frame_loop* f);
+// what icp_pmap_odometry_init refuses (pmap_frame.hip); own_batch: a frame launched by the asking batch itself is no obstacle
+int pmap_frame_init_check(icp_ctx* ctx, const icp_pmap_frame_config* cfg, bool own_batch);
 // what icp_odometry_init refuses (frame.hip); own_batch: a frame launched by the asking batch itself is no obstacle
 int frame_init_check(icp_ctx* ctx, const icp_frame_config* cfg, bool own_batch);
 // icp_frame_launch behind its checks and its upload (frame.hip)

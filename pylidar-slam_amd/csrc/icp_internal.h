@@ -612,6 +612,8 @@ struct icp_ctx {
     icp::Profile prof;
     // ---- one call per odometry frame (frame.hip: icp_odometry_init / icp_frame_launch / icp_frame_end)
     struct icp_frame_loop* frame = nullptr;    // created by icp_odometry_init, released by icp_destroy (frame_loop_release)
+    // ---- ... against the projective map (pmap_frame.hip: icp_pmap_odometry_init / icp_pmap_frame_launch / icp_pmap_frame_end)
+    struct icp_pmap_frame_loop* pframe = nullptr;  // created by icp_pmap_odometry_init, released by icp_destroy
 };
 
 // ---- B sequences per launch (api.hip: icp_batch_*)
@@ -658,6 +660,8 @@ inline int fail(icp_ctx* ctx, int code, const char* msg) {
 
 // ---- frame.hip
 void frame_loop_release(icp_ctx* ctx);
+// ---- pmap_frame.hip
+void pmap_frame_loop_release(icp_ctx* ctx);
 // ---- batch_frame.hip
 void batch_frames_release(icp_batch* batch);
 
@@ -748,6 +752,10 @@ int launch_procrustes_pass(icp_ctx* ctx, const float* tgt, const float* ref, con
 
 // ---- projection.hip
 // keep_keys: the z-buffer keys stay for the caller; rows_dev (optional): the same pixels as [H*W, 3] rows
+// a [3,H,W] vertex map in device memory -> its pixels as [H*W,3] rows (one launch)
+int vmap_rows_device(icp_ctx* ctx, const float* vmap_dev, float* rows_dev);
+// ... of `count` vertex maps of one image size in one launch, on first's stream
+int vmap_rows_batch_device(icp_ctx* first, int count, const float* const* vmap_dev, float* const* rows_dev);
 int project_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* vmap_dev, int32_t* index_dev, bool keep_keys = false,
                    float* rows_dev = nullptr);
 int project_pixels_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* rows_dev, float* cols_dev);

@@ -247,6 +247,54 @@ int project_batch_device(icp_ctx* const* ctxs, int count, const float* const* xy
     return ICP_OK;
 }
 
+// planar [3,H*W] vertex map -> the same pixels as [H*W,3] rows (vmap.permute(1, 2, 0).reshape(-1, 3): what sample_points reads,
+// slam/odometry/icp_odometry.py:301-308) for a caller-supplied vertex map, which no projection of the library has written
+__global__ void k_vmap_rows(const float* __restrict__ vmap, int npix, float* __restrict__ rows) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    rows[3 * p] = vmap[p];
+    rows[3 * p + 1] = vmap[npix + p];
+    rows[3 * p + 2] = vmap[2 * npix + p];
+}
+
+int vmap_rows_device(icp_ctx* ctx, const float* vmap_dev, float* rows_dev) {
+    const int npix = ctx->cfg.height * ctx->cfg.width;
+    if (npix <= 0) return ICP_OK;
+    hipLaunchKernelGGL(k_vmap_rows, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, ctx->stream, vmap_dev, npix, rows_dev);
+    ICP_HIP(ctx, hipGetLastError());
+    return ICP_OK;
+}
+
+// ... of B vertex maps in one launch: blockIdx.y = the member, its two pointers in the kernel-argument segment
+struct VmapRowsBatchArgs {
+    const float* vmap[ICP_BATCH_MAX_SEQUENCES];
+    float* rows[ICP_BATCH_MAX_SEQUENCES];
+};
+
+__global__ void k_vmap_rows_batch(VmapRowsBatchArgs a, int npix) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const float* __restrict__ vmap = a.vmap[blockIdx.y];
+    float* __restrict__ rows = a.rows[blockIdx.y];
+    rows[3 * p] = vmap[p];
+    rows[3 * p + 1] = vmap[npix + p];
+    rows[3 * p + 2] = vmap[2 * npix + p];
+}
+
+int vmap_rows_batch_device(icp_ctx* first, int count, const float* const* vmap_dev, float* const* rows_dev) {
+    const int npix = first->cfg.height * first->cfg.width;
+    if (npix <= 0 || count <= 0 || count > ICP_BATCH_MAX_SEQUENCES) return ICP_OK;
+    VmapRowsBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int b = 0; b < count; ++b) {
+        a.vmap[b] = vmap_dev[b];
+        a.rows[b] = rows_dev[b];
+    }
+    hipLaunchKernelGGL(k_vmap_rows_batch, dim3((unsigned)((npix + 255) / 256), count), dim3(256), 0, first->stream, a, npix);
+    ICP_HIP(first, hipGetLastError());
+    return ICP_OK;
+}
+
 int project_pixels_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* rows_dev, float* cols_dev) {
     if (n <= 0) return ICP_OK;
     hipLaunchKernelGGL(k_project_pixels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, xyz_dev, (int)n,

@@ -9,11 +9,12 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpFrameResult", "IcpBatchFrame", "load_library", "library_path",
-           "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
+__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpPmapFrameConfig", "IcpFrameResult", "IcpBatchFrame", "load_library", "library_path",
+           "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "FRAME_ROWS", "FRAME_VERTEX_MAP", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
 
 MEM_HOST, MEM_DEVICE = 0, 1
 TARGETS_ALL, TARGETS_SKIP_NULL = 0, 1
+FRAME_ROWS, FRAME_VERTEX_MAP = 0, 1  # icp_frame_layout
 # RIGID_ALIGNMENT modes of the reference (slam/odometry/alignment.py:200-208) -> icp_cost
 COSTS = {"point_to_plane_gauss_newton": 0, "point_to_point_gauss_newton": 1}
 
@@ -69,6 +70,13 @@ class IcpFrameConfig(C.Structure):
     _fields_ = [("voxel_size", C.c_double), ("threshold_trans", C.c_float), ("threshold_rot", C.c_float),
                 ("constant_velocity", C.c_int32), ("targets", C.c_int32), ("copy_cloud", C.c_int32),
                 ("stage_max_rows", C.c_int32)]
+
+
+class IcpPmapFrameConfig(C.Structure):
+    """icp_pmap_frame_config: the sequence settings of icp_pmap_odometry_init."""
+    _fields_ = [("voxel_size", C.c_double), ("threshold_trans", C.c_float), ("threshold_rot", C.c_float),
+                ("constant_velocity", C.c_int32), ("targets", C.c_int32), ("normals_kernel_size", C.c_int32),
+                ("copy_cloud", C.c_int32)]
 
 
 class IcpFrameResult(C.Structure):
@@ -150,6 +158,14 @@ EXPORTED_SYMBOLS = {
     "icp_odometry_init": (_INT, [_P, C.POINTER(IcpFrameConfig)]),
     "icp_frame_launch": (_INT, [_P, _P, _I64, _INT, _P, _P]),
     "icp_frame_end": (_INT, [_P, C.POINTER(IcpFrameResult), _P, _I64, C.POINTER(_I64), _INT, _P, _P]),
+    "icp_default_pmap_frame_config": (None, [C.POINTER(IcpPmapFrameConfig)]),
+    "icp_pmap_register_launch": (_INT, [_P, _P, _I64, _INT, _INT, _P]),
+    "icp_pmap_odometry_init": (_INT, [_P, C.POINTER(IcpPmapFrameConfig)]),
+    "icp_pmap_frame_launch": (_INT, [_P, _P, _I64, _INT, _INT, _P, _P]),
+    "icp_pmap_frame_end": (_INT, [_P, C.POINTER(IcpFrameResult), _P, _I64, C.POINTER(_I64), _INT, _P, _P]),
+    "icp_batch_pmap_odometry_init": (_INT, [_P, C.POINTER(IcpPmapFrameConfig)]),
+    "icp_batch_pmap_frame_launch": (_INT, [_P, C.POINTER(IcpBatchFrame), _INT, _INT]),
+    "icp_batch_pmap_frame_end": (_INT, [_P, C.POINTER(IcpFrameResult), _P, _P, _P, _INT, _P, _P]),
     "icp_batch_create": (_INT, [_P, C.c_int32, C.POINTER(_P)]),
     "icp_batch_destroy": (None, [_P]),
     "icp_batch_last_error": (C.c_char_p, [_P]),

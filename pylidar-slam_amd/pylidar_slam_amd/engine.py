@@ -12,8 +12,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (COSTS, IcpBatchFrame, IcpConfig, IcpFrameConfig, IcpFrameResult, IcpLibraryError, IcpPreprocessFrame,
-                   IcpRegisterResult, MEM_DEVICE, MEM_HOST, SCHEMES, STATUS_MESSAGES, TARGETS_ALL, TARGETS_SKIP_NULL)
+from ._lib import (COSTS, FRAME_ROWS, FRAME_VERTEX_MAP, IcpBatchFrame, IcpConfig, IcpFrameConfig, IcpFrameResult,
+                   IcpLibraryError, IcpPmapFrameConfig, IcpPreprocessFrame, IcpRegisterResult, MEM_DEVICE, MEM_HOST, SCHEMES,
+                   STATUS_MESSAGES, TARGETS_ALL, TARGETS_SKIP_NULL)
 
 Array = Union[np.ndarray, torch.Tensor]
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (device index) -> raw hipStream_t of torch's current stream
@@ -544,6 +545,16 @@ class IcpContext:
                                                 init, C.byref(res), losses, dxs))
         return self._result(res, losses, dxs)
 
+    def pmap_register_launch(self, points: Array, init_pose=None, skip_null: bool = False):
+        """`icp_pmap_register_launch`: `pmap_register` enqueued without waiting — every iteration on the stream, the stop
+        decided on the device, no host polls; `register_end()` collects it (the same result, bit for bit)."""
+        self._bind(points)
+        p, mem, keep = _ptr_mem(points)
+        self._keep_targets = [keep]
+        init = _pose16(init_pose if init_pose is not None else np.eye(4))
+        self._check(self._lib.icp_pmap_register_launch(self._h, p, int(keep.shape[0]), mem,
+                                                       TARGETS_SKIP_NULL if skip_null else TARGETS_ALL, init))
+
     # ---- alignment ---------------------------------------------------------------------------------------------------
     def _residual_buffer(self, n: int, mem: int, like, with_residuals: bool):
         if not with_residuals:
@@ -812,6 +823,92 @@ class IcpContext:
         out = np.empty((max(rows_cap, 1), 3), np.float32) if with_points else None
         rc = self._lib.icp_frame_end(self._h, C.byref(res), out.ctypes.data if out is not None else None, rows_cap,
                                      C.byref(count) if with_points else None, MEM_HOST, losses, dxs)
+        self._frame_keep = None
+        try:
+            self._check_registration(rc, res.reg, losses, dxs)
+        except AssertionError as e:  # (`cap` below the frame's rows: the frame is completed all the same)
+            e.rows, e.result, e.register = int(count.value), res, self._result(res.reg, losses, dxs)
+            raise
+        first = int(res.frame_index) == 0
+        points = out[:int(count.value)] if (out is not None and not first) else None
+        return FrameResult(self._result(res.reg, losses, dxs), int(res.frame_index), bool(res.key_frame), int(res.samples),
+                           int(res.inserted), points)
+
+    # ---- one call per odometry frame, projective local map -----------------------------------------------------------
+    def pmap_odometry_init(self, voxel_size: float = 0.0, threshold_trans: float = 0.1, threshold_rot: float = 0.3,
+                           constant_velocity: bool = True, targets: int = 0, normals_kernel_size: int = 5,
+                           copy_cloud: bool = True):
+        """`icp_pmap_odometry_init`: starts a sequence of `pmap_frame_launch` / `pmap_frame_end` on this context (empty
+        projective map, frame 0).  voxel_size > 0: the grid sample in front of every [N,3] frame; targets (for [N,3] frames)
+        0: the frame's rows, 1: the pixels of its vertex map; normals_kernel_size: the window of the inserted maps' normals;
+        the other settings as for `odometry_init`."""
+        cfg = IcpPmapFrameConfig()
+        self._lib.icp_default_pmap_frame_config(C.byref(cfg))
+        cfg.voxel_size, cfg.threshold_trans, cfg.threshold_rot = float(voxel_size), float(threshold_trans), float(threshold_rot)
+        cfg.constant_velocity, cfg.targets, cfg.copy_cloud = int(bool(constant_velocity)), int(targets), int(bool(copy_cloud))
+        cfg.normals_kernel_size = int(normals_kernel_size)
+        self._check(self._lib.icp_pmap_odometry_init(self._h, C.byref(cfg)))
+        self._pframe_cfg = cfg
+        self._frame_keep = None
+        self._frame_rows = 0
+
+    def pmap_frame_launch(self, data: Array, timestamps: Optional[Array] = None, init_pose=None):
+        """`icp_pmap_frame_launch`: one frame enqueued without waiting — [N,3] float32 rows (numpy: uploaded by the library;
+        a cuda tensor: used in place) or a cuda [3,H,W] / [1,3,H,W] vertex map (its pixels are the targets).  Device data
+        stays untouched until `pmap_frame_end`."""
+        if isinstance(data, torch.Tensor) and data.is_cuda and data.ndim in (3, 4):
+            self._bind(data)
+            vmap = data[0] if data.ndim == 4 else data
+            if data.ndim == 4 and data.shape[0] != 1:
+                raise AssertionError("Unexpected batched data format.")
+            if vmap.shape[0] != 3:
+                raise AssertionError(f"expected a [3,H,W] vertex map, got {tuple(data.shape)}")
+            vmap = vmap if vmap.dtype == torch.float32 and vmap.is_contiguous() else vmap.to(torch.float32).contiguous()
+            if timestamps is not None:
+                raise AssertionError("timestamps go with [N,3] rows, not with a vertex map")
+            n = int(vmap.shape[1] * vmap.shape[2])
+            self._check(self._lib.icp_pmap_frame_launch(self._h, vmap.data_ptr(), n, MEM_DEVICE, FRAME_VERTEX_MAP, None,
+                                                        _pose16(init_pose) if init_pose is not None else None))
+            self._frame_keep = (vmap, None)
+            self._frame_rows = n
+            return
+        self._bind(data)
+        if isinstance(data, torch.Tensor) and data.is_cuda:
+            pts = data if data.dtype == torch.float32 and data.is_contiguous() else data.to(torch.float32).contiguous()
+            ts = None
+            if timestamps is not None:
+                ts = torch.as_tensor(timestamps).to(pts.device, torch.float64).reshape(-1).contiguous()
+            mem, p, tp = MEM_DEVICE, pts.data_ptr(), ts.data_ptr() if ts is not None else None
+        else:
+            pts = data.numpy() if isinstance(data, torch.Tensor) else data
+            if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.flags.c_contiguous):
+                pts = np.ascontiguousarray(pts, dtype=np.float32)
+            ts = None
+            if timestamps is not None:
+                ts = np.ascontiguousarray(np.asarray(timestamps).reshape(-1), dtype=np.float64)
+            mem, p, tp = MEM_HOST, pts.ctypes.data, ts.ctypes.data if ts is not None else None
+        if pts.ndim != 2 or pts.shape[1] != 3 or (ts is not None and ts.shape[0] != pts.shape[0]):
+            raise AssertionError(f"expected [N,3] points (and [N] timestamps) or a [3,H,W] vertex map, got {tuple(pts.shape)}")
+        n = int(pts.shape[0])
+        self._check(self._lib.icp_pmap_frame_launch(self._h, p if n else None, n, mem, FRAME_ROWS, tp if n else None,
+                                                    _pose16(init_pose) if init_pose is not None else None))
+        self._frame_keep = (pts, ts) if mem == MEM_DEVICE else None
+        self._frame_rows = n
+
+    def pmap_frame_end(self, with_points: Optional[bool] = None, cap: Optional[int] = None) -> FrameResult:
+        """`icp_pmap_frame_end`: waits for the frame's registration alone, applies the key-frame test and enqueues the
+        projective map's update; returns what `frame_end` returns (`inserted`: 1 when a vertex map was appended)."""
+        if with_points is None:
+            with_points = bool(getattr(self, "_pframe_cfg", None) is not None and self._pframe_cfg.copy_cloud)
+        rows_cap = int(getattr(self, "_frame_rows", 0)) if cap is None else int(cap)
+        hist = max(1, int(self.config.max_num_alignments))
+        losses = (C.c_double * hist)()
+        dxs = (C.c_float * (6 * hist))()
+        res = IcpFrameResult()
+        count = C.c_int64(0)
+        out = np.empty((max(rows_cap, 1), 3), np.float32) if with_points else None
+        rc = self._lib.icp_pmap_frame_end(self._h, C.byref(res), out.ctypes.data if out is not None else None, rows_cap,
+                                          C.byref(count) if with_points else None, MEM_HOST, losses, dxs)
         self._frame_keep = None
         try:
             self._check_registration(rc, res.reg, losses, dxs)
@@ -1162,6 +1259,14 @@ class IcpBatch:
         self._frame_step = None
 
     def frame_launch(self, scans, timestamps=None, init_poses=None, skip=None):
+        self._launch_frames(scans, timestamps, init_poses, skip, False)
+
+    def pmap_frame_launch(self, frames, timestamps=None, init_poses=None, skip=None):
+        """`icp_batch_pmap_frame_launch`: as `frame_launch`, against the members' projective maps; `frames[b]`: [N,3] rows (all
+        numpy or all cuda) or — all members alike — cuda [3,H,W] / [1,3,H,W] vertex maps."""
+        self._launch_frames(frames, timestamps, init_poses, skip, True)
+
+    def _launch_frames(self, scans, timestamps, init_poses, skip, pmap):
         """`icp_batch_frame_launch`: `scans[b]` = member b's next frame ([N,3] float32; all numpy arrays — uploaded by the
         library through ONE pinned buffer — or all cuda tensors, used in place until `frame_end`); `timestamps[b]` ([N]
         float64 where the points live) or None; `init_poses[b]` (4x4) or None; `skip[b]`: the member sits this step out
@@ -1178,12 +1283,27 @@ class IcpBatch:
             raise AssertionError("the frames of a batched step must live in one memory space")
         if on_device:
             self.use_torch_stream()
+        vmaps = pmap and on_device and all(a.ndim in (3, 4) for a in active)
+        if pmap and not vmaps and any(isinstance(a, torch.Tensor) and a.ndim in (3, 4) for a in active):
+            raise AssertionError("the frames of a batched step are all rows or all cuda vertex maps")
         frames = (IcpBatchFrame * b)()
         keep, rows = [], [0] * b
         for i, (a, t, g, sk) in enumerate(zip(scans, timestamps, init_poses, skip)):
             f = frames[i]
             f.skip = 1 if sk else 0
             if sk:
+                continue
+            if vmaps:
+                vm = a[0] if a.ndim == 4 else a
+                if (a.ndim == 4 and a.shape[0] != 1) or vm.shape[0] != 3:
+                    raise AssertionError(f"member {i}: expected a [3,H,W] vertex map, got {tuple(a.shape)}")
+                vm = vm if vm.dtype == torch.float32 and vm.is_contiguous() else vm.to(torch.float32).contiguous()
+                pose = _pose16(g) if g is not None else None
+                f.xyz, f.n = vm.data_ptr(), int(vm.shape[1] * vm.shape[2])
+                f.timestamps = None if t is None else torch.as_tensor(t).to(vm.device, torch.float64).data_ptr()
+                f.init_pose = C.cast(pose, C.c_void_p) if pose is not None else None
+                keep.append((vm, t, pose))
+                rows[i] = int(f.n)
                 continue
             if on_device:
                 pts = a if a.dtype == torch.float32 and a.is_contiguous() else a.to(torch.float32).contiguous()
@@ -1203,10 +1323,34 @@ class IcpBatch:
             f.init_pose = C.cast(pose, C.c_void_p) if pose is not None else None
             keep.append((pts, ts, pose))
             rows[i] = n
-        self._check(self._lib.icp_batch_frame_launch(self._h, frames, MEM_DEVICE if on_device else MEM_HOST))
+        mem = MEM_DEVICE if on_device else MEM_HOST
+        if pmap:
+            self._check(self._lib.icp_batch_pmap_frame_launch(self._h, frames, mem, FRAME_VERTEX_MAP if vmaps else FRAME_ROWS))
+        else:
+            self._check(self._lib.icp_batch_frame_launch(self._h, frames, mem))
         self._frame_step = (keep if on_device else None, rows, skip)
 
-    def frame_end(self, with_points=None, cap=None):
+    def pmap_odometry_init(self, **kw):
+        """`icp_batch_pmap_odometry_init`: `IcpContext.pmap_odometry_init` on every member (the same keywords), every member
+        checked before any is restarted."""
+        cfg = IcpPmapFrameConfig()
+        self._lib.icp_default_pmap_frame_config(C.byref(cfg))
+        conv = {"voxel_size": float, "threshold_trans": float, "threshold_rot": float, "constant_velocity": lambda v: int(bool(v)),
+                "targets": int, "normals_kernel_size": int, "copy_cloud": lambda v: int(bool(v))}
+        for k, v in kw.items():
+            if k not in conv:
+                raise TypeError(f"pmap_odometry_init() got an unexpected keyword argument {k!r}")
+            setattr(cfg, k, conv[k](v))
+        self._check(self._lib.icp_batch_pmap_odometry_init(self._h, C.byref(cfg)))
+        for c in self.contexts:
+            c._pframe_cfg = cfg
+            c._frame_keep, c._frame_rows = None, 0
+
+    def pmap_frame_end(self, with_points=None, cap=None):
+        """`icp_batch_pmap_frame_end`: as `frame_end`, with ONE batched update of the projective maps."""
+        return self.frame_end(with_points, cap, _pmap=True)
+
+    def frame_end(self, with_points=None, cap=None, _pmap=False):
         """`icp_batch_frame_end`: one wait for all registrations, the key-frame tests, one batched map update.  A list with
         one `FrameResult` per member (None: the member sat the step out).  with_points: a flag or one per member (default:
         each member's `copy_cloud`).  A member whose registration failed raises `InvalidJacobianError` AFTER the step has
@@ -1217,7 +1361,8 @@ class IcpBatch:
         rows = step[1] if step else [0] * b
         skip = step[2] if step else [False] * b
         if with_points is None:
-            want = [bool(getattr(c, "_frame_cfg", None) is not None and c._frame_cfg.copy_cloud) for c in self.contexts]
+            attr = "_pframe_cfg" if _pmap else "_frame_cfg"
+            want = [bool(getattr(c, attr, None) is not None and getattr(c, attr).copy_cloud) for c in self.contexts]
         elif isinstance(with_points, (list, tuple)):
             want = [bool(v) for v in with_points]
         else:
@@ -1231,7 +1376,8 @@ class IcpBatch:
         out_ptrs = (C.c_void_p * b)(*[o.ctypes.data if o is not None else None for o in outs])
         cap_arr = (C.c_int64 * b)(*caps)
         counts = (C.c_int64 * b)()
-        rc = self._lib.icp_batch_frame_end(self._h, res, out_ptrs, cap_arr, counts, MEM_HOST, losses, dxs)
+        end = self._lib.icp_batch_pmap_frame_end if _pmap else self._lib.icp_batch_frame_end
+        rc = end(self._h, res, out_ptrs, cap_arr, counts, MEM_HOST, losses, dxs)
         if rc == _lib.ICP_ERR_INVALID_ARGUMENT and \
                 self._lib.icp_batch_last_error(self._h).decode().endswith("(nothing was changed)"):
             self._check(rc)  # refused: the step (if any) still awaits its end

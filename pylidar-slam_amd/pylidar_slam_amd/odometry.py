@@ -933,6 +933,10 @@ class MI355XICPConfig:
     # `MI355XICPFrameToModelBatch`: a step of all members is ONE pair of calls (icp_batch_frame_launch + icp_batch_frame_end),
     # and numpy [N, 3] frames are accepted on that route
     one_call_frame: bool = False
+    # The same for the projective local map (PF2M): a frame is icp_pmap_frame_launch + icp_pmap_frame_end — the same poses,
+    # iterations, key frames, clouds, window and model, bit for bit.  numpy [N, 3], cuda [N, 3] and cuda [3, H, W] /
+    # [1, 3, H, W] vertex-map frames; anything else is refused with the reason, and so is the flag on a kd-tree style map
+    one_call_projective_frame: bool = False
 
 
 def _get(obj, key, default=None):
@@ -1014,6 +1018,14 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
             assert_debug(not bool(_get(config, "compact_sparse_vertex_map", False)),
                          "one_call_frame: compact_sparse_vertex_map is a schedule of the per-call path only")
             assert_debug(hasattr(self.ctx, "frame_launch"), "one_call_frame needs the library's frame calls")
+        self._one_call_pmap = bool(_get(config, "one_call_projective_frame", False))
+        if self._one_call_pmap:
+            assert_debug(self._projective, "one_call_projective_frame: the projective frame calls of the library run the "
+                                           "projective local map; the kd-tree style map has one_call_frame")
+            assert_debug(not bool(_get(config, "compact_sparse_vertex_map", False)),
+                         "one_call_projective_frame: compact_sparse_vertex_map is a schedule of the per-call path only")
+            assert_debug(hasattr(self.ctx, "pmap_frame_launch"),
+                         "one_call_projective_frame needs the library's projective frame calls")
 
     def init(self):  # :128-145
         super().init()
@@ -1139,6 +1151,8 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         self.ctx.use_torch_stream()
         if self._one_call:
             return self._one_call_next_frame(data_dict)
+        if self._one_call_pmap:
+            return self._one_call_pmap_next_frame(data_dict)
         self._read_input(data_dict)
         if self._iter == 0:
             eye = np.eye(4, dtype=np.float32)
@@ -1237,6 +1251,74 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
                                                                                  np.float64)))  # :200-202
         if want_rows and not is_numpy:
             tgt_np_pc = res.points.copy()
+        data_dict[self.pointcloud_key()] = tgt_np_pc if want_rows else data_dict["distorted"]  # :243
+        data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+        self._iter += 1
+
+    def _one_call_pmap_next_frame(self, data_dict: dict):
+        """`one_call_projective_frame`: the frame through icp_pmap_frame_launch + icp_pmap_frame_end.  The library uploads a
+        numpy frame, projects (or transposes a vertex map into target rows), compacts and copies out `odometry_pc`, registers
+        against the projective map from `init_rpose`, applies the key-frame test of `__update_map` and updates the map; what
+        stays here is the pose chain and the outputs written to the dict.  As on `_one_call_next_frame` the guess is the
+        dict's `init_rpose`, handed over with every frame."""
+        key = self.config.data_key
+        assert_debug(key in data_dict, f"Could not find the key `{key}` in the input dictionary.\n"
+                                       f"With keys : {data_dict.keys()}). Set the parameter "
+                                       f"`slam.odometry.data_key` to the desired key")
+        data = data_dict[key]
+        is_numpy = isinstance(data, np.ndarray)
+        is_cuda = isinstance(data, torch.Tensor) and data.is_cuda
+        is_vmap = is_cuda and data.ndim in (3, 4)
+        assert_debug(is_numpy or (is_cuda and data.ndim in (2, 3, 4)),
+                     "one_call_projective_frame covers numpy [N, 3], cuda [N, 3] and cuda [3, H, W] / [1, 3, H, W] frames: "
+                     "anything else (a cpu tensor) goes through the per-call path (one_call_projective_frame=False), got "
+                     f"{type(data).__name__} {tuple(getattr(data, 'shape', ()))}")
+        if is_vmap:
+            assert_debug(data.ndim == 3 or data.shape[0] == 1, "Unexpected batched data format.")
+            assert_debug(data.shape[-3] == 3 and tuple(data.shape[-2:]) == (int(self.projector.height), int(self.projector.width)),
+                         f"expected a [3, {self.projector.height}, {self.projector.width}] vertex map, got {tuple(data.shape)}")
+        else:
+            assert_debug(data.ndim == 2 and data.shape[1] == 3, f"expected [N, 3], got {tuple(data.shape)}")
+        if is_numpy:
+            self._sample_pointcloud = True  # sticky (:330)
+        targets = 0 if self._sample_pointcloud else 1  # sample_points :301-308 (a vertex map's targets are its pixels anyway)
+        want_rows = "distorted" not in data_dict  # (:210-213)
+        from_device = want_rows and not is_numpy
+        if self._iter == 0:
+            self.ctx.pmap_odometry_init(voxel_size=0.0, threshold_trans=self._register_threshold_trans,
+                                        threshold_rot=self._register_threshold_rot, constant_velocity=False, targets=targets,
+                                        normals_kernel_size=int(self.local_map.normals_kernel_size), copy_cloud=from_device)
+            self._one_call_targets = targets
+        assert_debug(is_vmap or targets == self._one_call_targets,
+                     "one_call_projective_frame: numpy and tensor frames were mixed within one sequence (the targets of a "
+                     "sequence are its rows or its pixels)")
+        self._host_rows = None
+        if is_numpy:
+            self._host_rows = data if data.dtype == np.float32 and data.flags.c_contiguous else \
+                np.ascontiguousarray(data, dtype=np.float32)
+        self.ctx.pmap_frame_launch(self._host_rows if is_numpy else data, None,
+                                   self._initial_pose(data_dict) if self._iter > 0 else None)
+        tgt_np_pc = self._rows_to_host(None) if (want_rows and is_numpy and self._iter > 0) else None  # GPU busy meanwhile
+        res = self.ctx.pmap_frame_end(with_points=from_device and self._iter > 0)  # raises before the map is touched (:286)
+        if res.key_frame:
+            # (`get_last_frame`: a vertex map handed in is the newest stored map; for rows the library's projection is repeated
+            # here — the same pixels — behind the frame, off its critical path)
+            self.local_map._last_vmap = (data[0] if data.ndim == 4 else data) if is_vmap else \
+                self.ctx.project(self._host_rows if is_numpy else data)
+        if self._iter == 0:
+            self.relative_poses.append(np.eye(4, dtype=np.float32)[None])
+            self.absolute_poses.append(np.eye(4, dtype=np.float64))
+            self._iter += 1
+            return
+        self.last_result = res.register
+        pose, params = res.register.pose, res.register.params
+        self._delta_since_map_update = np.eye(4, dtype=np.float32) if res.key_frame else \
+            (self._delta_since_map_update @ pose).astype(np.float32)
+        self.relative_poses.append(pose[None].copy())
+        self.absolute_poses.append(self.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64),
+                                                                                 np.float64)))  # :200-202
+        if want_rows and not is_numpy:
+            tgt_np_pc = res.points  # (a view of the fresh array the call filled: nobody else holds it)
         data_dict[self.pointcloud_key()] = tgt_np_pc if want_rows else data_dict["distorted"]  # :243
         data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
         self._iter += 1
@@ -1387,6 +1469,12 @@ class MI355XICPFrameToModelBatch:
         self._one_call_targets = None
         if self._one_call:
             assert_debug(hasattr(self.batch, "frame_launch"), "one_call_frame needs the library's batched frame calls")
+        # `one_call_projective_frame`: the same for the projective map (icp_batch_pmap_frame_launch + icp_batch_pmap_frame_end);
+        # the members were built with the flag and have refused a kd-tree style map
+        self._one_call_pmap = bool(_get(self.config, "one_call_projective_frame", False))
+        if self._one_call_pmap:
+            assert_debug(hasattr(self.batch, "pmap_frame_launch"),
+                         "one_call_projective_frame needs the library's batched projective frame calls")
 
     def __len__(self):
         return len(self.members)
@@ -1410,6 +1498,8 @@ class MI355XICPFrameToModelBatch:
         beginning = time.time()
         if self._one_call:
             self._process_one_call(data_dicts)
+        elif self._one_call_pmap:
+            self._process_one_call_pmap(data_dicts)
         else:
             self._process(data_dicts)
         self.elapsed.append(time.time() - beginning)
@@ -1485,6 +1575,84 @@ class MI355XICPFrameToModelBatch:
             m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64), np.float64)))
             if want[b] and not is_numpy:
                 pcs[b] = res.points.copy()
+            d[m.pointcloud_key()] = pcs[b] if want[b] else d["distorted"]  # :243
+            d[m.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+            m._iter += 1
+        self._iter += 1
+        if error is not None:
+            raise error
+
+    def _process_one_call_pmap(self, data_dicts):
+        """`one_call_projective_frame`: the step through icp_batch_pmap_frame_launch + icp_batch_pmap_frame_end — per member what
+        `MI355XICPFrameToModel._one_call_pmap_next_frame` does with the single calls.  numpy [N, 3], cuda [N, 3] or cuda
+        [3, H, W] / [1, 3, H, W] frames, all members alike.  A member whose registration fails raises `InvalidJacobianError`
+        after the other members have completed their frame."""
+        members = self.members
+        assert_debug(len(data_dicts) == len(members), f"expected {len(members)} frames, got {len(data_dicts)}")
+        key = self.config.data_key
+        for d in data_dicts:
+            assert_debug(key in d, f"Could not find the key `{key}` in the input dictionary.")
+        frames = [d[key] for d in data_dicts]
+        is_numpy = all(isinstance(f, np.ndarray) for f in frames)
+        is_cuda = all(isinstance(f, torch.Tensor) and f.is_cuda for f in frames)
+        is_vmap = is_cuda and all(f.ndim in (3, 4) for f in frames)
+        assert_debug(is_numpy or is_vmap or (is_cuda and all(f.ndim == 2 for f in frames)),
+                     "one_call_projective_frame covers numpy [N, 3], cuda [N, 3] and cuda [3, H, W] / [1, 3, H, W] frames (all "
+                     "members alike): anything else (a cpu tensor) goes through the per-call path, got "
+                     f"{[(type(f).__name__, tuple(getattr(f, 'shape', ()))) for f in frames]}")
+        if not is_vmap:
+            for f in frames:
+                assert_debug(f.ndim == 2 and f.shape[1] == 3, f"expected [N, 3], got {tuple(f.shape)}")
+        if is_numpy:
+            for m in members:
+                m._sample_pointcloud = True  # sticky (:330)
+        targets = 0 if members[0]._sample_pointcloud else 1  # sample_points :301-308
+        want = ["distorted" not in d for d in data_dicts]  # (:210-213)
+        first = self._iter == 0
+        if first:
+            self.batch.use_torch_stream()
+            self.batch.pmap_odometry_init(voxel_size=0.0, threshold_trans=members[0]._register_threshold_trans,
+                                          threshold_rot=members[0]._register_threshold_rot, constant_velocity=False,
+                                          targets=targets, normals_kernel_size=int(members[0].local_map.normals_kernel_size),
+                                          copy_cloud=any(want) and not is_numpy)
+            self._one_call_targets = targets
+        assert_debug(is_vmap or targets == self._one_call_targets,
+                     "one_call_projective_frame: numpy and tensor frames were mixed within one sequence (the targets of a "
+                     "sequence are its rows or its pixels)")
+        if is_numpy:
+            frames = [f if f.dtype == np.float32 and f.flags.c_contiguous else np.ascontiguousarray(f, dtype=np.float32)
+                      for f in frames]
+        else:
+            self.batch.use_torch_stream()
+        self.batch.pmap_frame_launch(frames, None, None if first else [m._initial_pose(d) for m, d in zip(members, data_dicts)])
+        pcs = [None] * len(members)
+        if is_numpy and not first:  # (`odometry_pc` of a numpy frame is made from the host rows: GPU busy meanwhile)
+            for b, (m, f, w) in enumerate(zip(members, frames, want)):
+                m._host_rows = f
+                pcs[b] = m._rows_to_host(None) if w else None
+        error = None
+        try:
+            results = self.batch.pmap_frame_end(with_points=[w and not is_numpy and not first for w in want])
+        except InvalidJacobianError as e:  # (raised behind the step: the healthy members have completed their frame)
+            error, results = e, e.results
+        for b, (m, res, d, f) in enumerate(zip(members, results, data_dicts, frames)):
+            if res is None:
+                continue
+            if res.key_frame:
+                m.local_map._last_vmap = (f[0] if f.ndim == 4 else f) if is_vmap else m.ctx.project(f)
+            if first:
+                m.relative_poses.append(np.eye(4, dtype=np.float32)[None])
+                m.absolute_poses.append(np.eye(4, dtype=np.float64))
+                m._iter += 1
+                continue
+            m.last_result = res.register
+            pose, params = res.register.pose, res.register.params
+            m._delta_since_map_update = np.eye(4, dtype=np.float32) if res.key_frame else \
+                (m._delta_since_map_update @ pose).astype(np.float32)
+            m.relative_poses.append(pose[None].copy())
+            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64), np.float64)))
+            if want[b] and not is_numpy:
+                pcs[b] = res.points  # (a view of the fresh array the call filled: nobody else holds it)
             d[m.pointcloud_key()] = pcs[b] if want[b] else d["distorted"]  # :243
             d[m.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
             m._iter += 1
