@@ -383,7 +383,10 @@ int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int ta
  * correspondences; one Gauss-Newton step from x0 = 0 (slam/common/optimization.py:296-344).
  * dx_out[6], pose_out[16] = build_pose_matrix(dx), loss_out = sum (w r)^2, normal_eq_out (optional) = 32 doubles:
  * 21 upper-triangular JtJ, 6 Jtr, sum (w r)^2, sum r^2, row count, 2 pad; residuals_out (optional, [n] float, in the
- * memory space `mem` of the inputs) = (w r)^2 per row, the residual tensor `align` returns (optimization.py:342-344). */
+ * memory space `mem` of the inputs) = (w r)^2 per row, the residual tensor `align` returns (optimization.py:342-344).
+ * The outputs are written before ICP_ERR_INVALID_JACOBIAN is returned (dx = 0, the loss and the sums of the rows).
+ * Refused with ICP_ERR_INVALID_ARGUMENT ("registration in progress") between icp_register_begin / icp_register_launch and
+ * icp_register_end: the call stages into the target, partial-row and normal-equation buffers of the registration. */
 int icp_align_point_to_plane(icp_ctx* ctx, const float* ref_points, const float* tgt_points, const float* ref_normals,
                              int64_t n, int mem, float dx_out[6], float pose_out[16], double* loss_out,
                              double* normal_eq_out, float* residuals_out);
@@ -391,12 +394,14 @@ int icp_align_point_to_plane(icp_ctx* ctx, const float* ref_points, const float*
 /* GaussNewtonPointToPointAlignment.align (slam/odometry/alignment.py:143-189) on given correspondences: one
  * Gauss-Newton step of PointToPointCost (slam/common/optimization.py:458-560) linearised at x0 (NULL = zeros; with
  * `initialize_with_svd` the caller passes from_pose_matrix(icp_weighted_procrustes(...))).  params_out = x0 + dx,
- * pose_out = build_pose_matrix(params_out); loss_out / normal_eq_out / residuals_out as above. */
+ * pose_out = build_pose_matrix(params_out); loss_out / normal_eq_out / residuals_out as above.  Refused with "registration
+ * in progress" like icp_align_point_to_plane. */
 int icp_align_point_to_point(icp_ctx* ctx, const float* ref_points, const float* tgt_points, int64_t n, int mem,
                              const float x0[6], float params_out[6], float pose_out[16], double* loss_out,
                              double* normal_eq_out, float* residuals_out);
 /* weighted_procrustes (slam/common/registration.py:15-74): closed-form rigid transform target -> reference.  weights
- * [n] float32 or NULL (ones); as in the reference they enter the centroids only.  pose_out row-major 4x4 float64. */
+ * [n] float32 or NULL (ones); as in the reference they enter the centroids only.  pose_out row-major 4x4 float64.
+ * Refused with "registration in progress" like icp_align_point_to_plane. */
 int icp_weighted_procrustes(icp_ctx* ctx, const float* tgt_points, const float* ref_points, const float* weights,
                             int64_t n, int mem, double pose_out[16]);
 

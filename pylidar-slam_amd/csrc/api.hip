@@ -1305,6 +1305,9 @@ int icp_align_point_to_plane(icp_ctx* ctx, const float* ref_points, const float*
                              double* normal_eq_out, float* residuals_out) {
     DeviceGuard device_guard(ctx);
     if (!ctx || n <= 0 || !ref_points || !tgt_points || !ref_normals) return ICP_ERR_INVALID_ARGUMENT;
+    // the seams stage into the buffers of a registration (targets, partial rows, normal equations): refused while one is
+    // enqueued or uncollected, like icp_map_update / icp_nearest_neighbor_search
+    if (ctx->in_registration || ctx->result_pending()) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     int rc = ensure_state(ctx);
     if (rc) return rc;
     const void *r, *t, *nr;
@@ -1341,6 +1344,9 @@ int icp_align_point_to_point(icp_ctx* ctx, const float* ref_points, const float*
                              double* normal_eq_out, float* residuals_out) {
     DeviceGuard device_guard(ctx);
     if (!ctx || n <= 0 || !ref_points || !tgt_points) return ICP_ERR_INVALID_ARGUMENT;
+    // the seams stage into the buffers of a registration (targets, partial rows, normal equations): refused while one is
+    // enqueued or uncollected, like icp_map_update / icp_nearest_neighbor_search
+    if (ctx->in_registration || ctx->result_pending()) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     int rc = ensure_state(ctx);
     if (rc) return rc;
     const void *r, *t;
@@ -1427,6 +1433,9 @@ int icp_weighted_procrustes(icp_ctx* ctx, const float* tgt_points, const float* 
                             int64_t n, int mem, double pose_out[16]) {
     DeviceGuard device_guard(ctx);
     if (!ctx || n <= 0 || !ref_points || !tgt_points || !pose_out) return ICP_ERR_INVALID_ARGUMENT;
+    // the seams stage into the buffers of a registration (targets, partial rows, normal equations): refused while one is
+    // enqueued or uncollected, like icp_map_update / icp_nearest_neighbor_search
+    if (ctx->in_registration || ctx->result_pending()) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     int rc = ensure_state(ctx);
     if (rc) return rc;
     const void *r, *t, *w = nullptr;

@@ -565,6 +565,19 @@ class IcpContext:
         buf = np.empty(n, np.float32)
         return buf, buf.ctypes.data
 
+    def _aligned(self, rc, pose, params, loss, neq, res, with_residuals):
+        """The result tuple of an align call; an InvalidJacobianError carries it as `result` (the library writes every
+        output before it returns that status: dx = 0, the loss and the sums of the rows, the residual vector)."""
+        out = (np.array(pose, np.float32).reshape(4, 4), np.array(params, np.float32), float(loss.value),
+               np.array(neq, np.float64))
+        out = out + (res,) if with_residuals else out
+        try:
+            self._check(rc)
+        except InvalidJacobianError as e:
+            e.result = out
+            raise
+        return out
+
     def align_point_to_plane(self, ref_points: Array, tgt_points: Array, ref_normals: Array,
                              with_residuals: bool = False):
         """One Gauss-Newton point-to-plane step: (pose [4,4], dx [6], loss, normal equations [32] f64[, residuals [n]
@@ -583,11 +596,8 @@ class IcpContext:
         loss = C.c_double(0)
         neq = (C.c_double * 32)()
         res, res_ptr = self._residual_buffer(n, mem_r, kr, with_residuals)
-        self._check(self._lib.icp_align_point_to_plane(self._h, r, t, nn, n, mem_r, dx, pose, C.byref(loss), neq,
-                                                       res_ptr))
-        out = (np.array(pose, np.float32).reshape(4, 4), np.array(dx, np.float32), float(loss.value),
-               np.array(neq, np.float64))
-        return out + (res,) if with_residuals else out
+        rc = self._lib.icp_align_point_to_plane(self._h, r, t, nn, n, mem_r, dx, pose, C.byref(loss), neq, res_ptr)
+        return self._aligned(rc, pose, dx, loss, neq, res, with_residuals)
 
     def align_point_to_point(self, ref_points: Array, tgt_points: Array, x0=None, with_residuals: bool = False):
         """One Gauss-Newton point-to-point step linearised at x0 ([6] or None = zeros):
@@ -606,11 +616,8 @@ class IcpContext:
         loss = C.c_double(0)
         neq = (C.c_double * 32)()
         res, res_ptr = self._residual_buffer(n, mem_r, kr, with_residuals)
-        self._check(self._lib.icp_align_point_to_point(self._h, r, t, n, mem_r, x, params, pose, C.byref(loss), neq,
-                                                       res_ptr))
-        out = (np.array(pose, np.float32).reshape(4, 4), np.array(params, np.float32), float(loss.value),
-               np.array(neq, np.float64))
-        return out + (res,) if with_residuals else out
+        rc = self._lib.icp_align_point_to_point(self._h, r, t, n, mem_r, x, params, pose, C.byref(loss), neq, res_ptr)
+        return self._aligned(rc, pose, params, loss, neq, res, with_residuals)
 
     def weighted_procrustes(self, tgt_points: Array, ref_points: Array, weights=None) -> np.ndarray:
         """`weighted_procrustes` (slam/common/registration.py:15-74): [4,4] float64 transform target -> reference."""
