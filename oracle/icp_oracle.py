@@ -159,19 +159,42 @@ def kitti_correct_scan(scan: np.ndarray) -> np.ndarray:
     return (rot * p.astype(F64)[:, None, :]).sum(axis=2)
 
 
+def rotation_axis_angle(rot: np.ndarray):
+    """(axis, theta) of the rotation scipy's `Rotation.from_matrix` yields for a 3x3 block (the scipy this oracle is pinned
+    on, 1.15): a block that fails np.isclose(M M^T, I, atol=1e-12) — a float32 pose is 6e-8 from a rotation — is replaced
+    by U V^T of its SVD (the orthogonal Procrustes solution), then Markley's quaternion (J. Guidance 31.2, 2008): the
+    largest of the trace and the diagonal picks the formula, the result is normalised.  theta = 2 atan2(|xyz|, w)."""
+    m = np.asarray(rot, dtype=np.float64)
+    if not np.all(np.isclose(m @ m.T, np.eye(3), atol=1e-12)):
+        u, _, vt = np.linalg.svd(m)
+        m = u @ vt
+    dec = [m[0, 0], m[1, 1], m[2, 2], m[0, 0] + m[1, 1] + m[2, 2]]
+    c = int(np.argmax(dec))
+    q = np.zeros(4)
+    if c != 3:
+        i, j, k = c, (c + 1) % 3, (c + 2) % 3
+        q[i] = 1 - dec[3] + 2 * m[i, i]
+        q[j] = m[j, i] + m[i, j]
+        q[k] = m[k, i] + m[i, k]
+        q[3] = m[k, j] - m[j, k]
+    else:
+        q[:3] = m[2, 1] - m[1, 2], m[0, 2] - m[2, 0], m[1, 0] - m[0, 1]
+        q[3] = 1 + dec[3]
+    q = q / np.linalg.norm(q)
+    q = -q if q[3] < 0 else q
+    nv = np.linalg.norm(q[:3])
+    return (q[:3] / nv if nv > 0 else np.zeros(3)), 2.0 * np.arctan2(nv, q[3])
+
+
 def distort(pc: np.ndarray, timestamps: np.ndarray, rpose: np.ndarray) -> np.ndarray:
     """reference slam/preprocessing.py:144-191 (`Distortion.filter`): every point is moved by the
     fraction alpha = (t - t_min) / (t_max - t_min) of the initial motion estimate: rotation slerp(I, R, alpha)
-    (scipy `Slerp`, i.e. exp(alpha * log R)) and translation alpha * t.  float64 out, like the reference's einsum."""
+    (scipy `Slerp`, i.e. exp(alpha * log R') with R' = from_matrix(R): rotation_axis_angle) and translation alpha * t.
+    float64 out, like the reference's einsum.  (tests/preprocess_audit.py holds it to scipy's own Slerp.)"""
     ts = np.asarray(timestamps, dtype=np.float64).reshape(-1)
     diff = ts.max() - ts.min()
     alpha = ts * 0 if diff == 0.0 else (ts - ts.min()) / diff  # :177-179
-    rot = np.asarray(rpose)[:3, :3].astype(np.float64)
-    # log map: (R - R^T) / 2 = sin(theta) [axis]x, trace = 1 + 2 cos(theta)   (theta < pi)
-    v = 0.5 * np.array([rot[2, 1] - rot[1, 2], rot[0, 2] - rot[2, 0], rot[1, 0] - rot[0, 1]])
-    nv = np.linalg.norm(v)
-    theta = np.arctan2(nv, 0.5 * (np.trace(rot) - 1.0))
-    axis = v / nv if nv > 0 else np.zeros(3)
+    axis, theta = rotation_axis_angle(np.asarray(rpose)[:3, :3].astype(np.float64))
     phi = alpha * theta
     p = np.asarray(pc).astype(np.float64)
     c, s_ = np.cos(phi)[:, None], np.sin(phi)[:, None]

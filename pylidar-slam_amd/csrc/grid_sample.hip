@@ -786,7 +786,7 @@ int voxel_statistics_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, doubl
 // ---------------------------------------------------------------------------------------------------------------------
 // De-skew (`Distortion.filter`, slam/preprocessing.py:144-191): timestamp range by a two-level f64 min/max reduction,
 // then per point the Rodrigues rotation by alpha * theta about the axis of the initial motion + alpha * translation,
-// all in float64 like the reference (scipy Slerp + a float64 einsum).
+// all in float64 like the reference (scipy Slerp + a float64 einsum); axis and theta: distort_arg below.
 // ---------------------------------------------------------------------------------------------------------------------
 // (the body of k_minmax_f64 and of k_minmax_f64_batch)
 __device__ __forceinline__ void minmax_f64_body(const double* __restrict__ v, int n, double* __restrict__ part) {
@@ -854,19 +854,73 @@ __global__ void k_distort(const float* __restrict__ xyz, const double* __restric
 
 static constexpr int DISTORT_PARTS = 64;  // workgroups of the timestamp min / max
 
-// log map of the rotation: (R - R^T) / 2 = sin(theta) [axis]x, trace = 1 + 2 cos(theta)
+// Axis and angle of the rotation the reference de-skews by: scipy's Rotation.from_matrix of the 3x3 block handed over, as
+// Slerp then scales it.  An exact rotation goes straight to the quaternion; a matrix that is not one — the frame loop's
+// guess is a FLOAT32 pose, 6e-8 from a rotation — is first replaced by its orthogonal factor (the U V^T of scipy's SVD,
+// here by Newton's iteration X <- (X + X^-T) / 2: quadratic, no LAPACK), under scipy's own test: |M M^T - I| <= 1e-12
+// + 1e-5 |I| entry by entry.  Then Markley's quaternion (J. Guidance 31.2, 2008): the largest of the trace and the diagonal
+// picks the formula, the result is normalised; theta = 2 atan2(|xyz|, w), w >= 0.  (Earlier the axis and the angle
+// came from (R - R^T) / 2 and the trace of the RAW matrix: right for an exact rotation, 6e-8 m at theta = 0.05 and 3e-5 m
+// at theta = 3 off the reference for a float32 pose, and without an axis at theta = pi.)
+static void polar_rotation3(double m[3][3]) {
+    for (int it = 0; it < 30; ++it) {
+        double c[3][3];  // the transposed inverse: cofactors / det
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j)
+                c[i][j] = m[(i + 1) % 3][(j + 1) % 3] * m[(i + 2) % 3][(j + 2) % 3] -
+                          m[(i + 1) % 3][(j + 2) % 3] * m[(i + 2) % 3][(j + 1) % 3];
+        const double det = m[0][0] * c[0][0] + m[0][1] * c[0][1] + m[0][2] * c[0][2];
+        if (!(fabs(det) > 0.0)) return;  // (a singular block: nothing to de-skew by; scipy refuses it)
+        double change = 0.0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const double x = 0.5 * (m[i][j] + c[i][j] / det);
+                change = std::max(change, fabs(x - m[i][j]));
+                m[i][j] = x;
+            }
+        if (change <= 8.9e-16) break;  // 4 eps
+    }
+}
+
 static DistortArg distort_arg(const double* rel_pose16) {
-    const double* R = rel_pose16;
-    const double vx = 0.5 * (R[9] - R[6]), vy = 0.5 * (R[2] - R[8]), vz = 0.5 * (R[4] - R[1]);
-    const double nv = sqrt(vx * vx + vy * vy + vz * vz);
+    const double* P = rel_pose16;
+    double m[3][3] = {{P[0], P[1], P[2]}, {P[4], P[5], P[6]}, {P[8], P[9], P[10]}};
+    bool orthogonal = true;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double g = m[i][0] * m[j][0] + m[i][1] * m[j][1] + m[i][2] * m[j][2], e = i == j ? 1.0 : 0.0;
+            if (!(fabs(g - e) <= 1e-12 + 1e-5 * e)) orthogonal = false;
+        }
+    if (!orthogonal) polar_rotation3(m);
+    const double dec[4] = {m[0][0], m[1][1], m[2][2], m[0][0] + m[1][1] + m[2][2]};
+    int choice = 0;
+    for (int k = 1; k < 4; ++k)
+        if (dec[k] > dec[choice]) choice = k;
+    double q[4];
+    if (choice != 3) {
+        const int i = choice, j = (i + 1) % 3, k = (j + 1) % 3;
+        q[i] = 1.0 - dec[3] + 2.0 * m[i][i];
+        q[j] = m[j][i] + m[i][j];
+        q[k] = m[k][i] + m[i][k];
+        q[3] = m[k][j] - m[j][k];
+    } else {
+        q[0] = m[2][1] - m[1][2];
+        q[1] = m[0][2] - m[2][0];
+        q[2] = m[1][0] - m[0][1];
+        q[3] = 1.0 + dec[3];
+    }
+    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double sign = q[3] < 0 ? -1.0 : 1.0;
+    for (int k = 0; k < 4; ++k) q[k] = nq > 0 ? sign * q[k] / nq : 0.0;
+    const double nv = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
     DistortArg a;
-    a.theta = atan2(nv, 0.5 * (R[0] + R[5] + R[10] - 1.0));
-    a.axis[0] = nv > 0 ? vx / nv : 0.0;
-    a.axis[1] = nv > 0 ? vy / nv : 0.0;
-    a.axis[2] = nv > 0 ? vz / nv : 0.0;
-    a.t[0] = R[3];
-    a.t[1] = R[7];
-    a.t[2] = R[11];
+    a.theta = 2.0 * atan2(nv, q[3]);
+    a.axis[0] = nv > 0 ? q[0] / nv : 0.0;
+    a.axis[1] = nv > 0 ? q[1] / nv : 0.0;
+    a.axis[2] = nv > 0 ? q[2] / nv : 0.0;
+    a.t[0] = P[3];
+    a.t[1] = P[7];
+    a.t[2] = P[11];
     return a;
 }
 

@@ -117,7 +117,8 @@ def test_voxel_hash_and_grid_sample(torch_cuda, O, golden_components):
     same = np.tile(np.array([[1.0, 2.0, 3.0]], np.float32), (100, 1))
     p1, i1 = ctx.grid_sample(same, 0.3)
     np.testing.assert_array_equal(i1, [0])
-    # large coordinates: int64 wrap-around identical to numpy
+    # large coordinates: |voxel| ~ 1e9, |hash| ~ 1e17 — large, but the int64 sums do NOT wrap here; wrapping sums and keys over
+    # the full 64-bit range are case (d) of tests/test_gpu_preprocess_audit.py (preprocess_audit.wrap_case)
     rng = np.random.default_rng(5)
     big = (rng.normal(size=(5000, 3)) * 1e6).astype(np.float32)
     _, hb = ctx.voxel_hash(big, 1e-3)
