@@ -323,6 +323,35 @@ int icp_voxel_statistics(icp_ctx* ctx, const float* xyz, int64_t n, int mem, dou
 int icp_distort(icp_ctx* ctx, const float* xyz, const double* timestamps, int64_t n, int mem, const double rel_pose[16],
                 double* xyz_out, int out_mem);
 
+/* ---- time stamps of a rotating sensor: estimate_timestamps (slam/common/geometry.py:443-466) ------------------------
+ * rows [n, stride] float32 (stride = 3 for xyz rows, 4 for the x, y, z, reflectance records of a .bin scan) ->
+ * timestamps [n] float64 in [0, 1]: the producer of the `timestamps` pointer icp_distort, the four frame calls and
+ * icp_batch_preprocess take (in device memory: no host round trip).  ARITHMETIC  The reference, on float32 rows, stays in
+ * float32:  phi = arctan2(y, x) * (clockwise ? -1 : +1);  phi -= float32(phi_0);  phi += float32(2 pi) where phi < 0;
+ * t = (phi - min phi) / (max phi - min phi).  numpy's float32 arctan2 is not correctly rounded (one ulp, 2.4e-7, off the
+ * rounded float64 value in about a third of the rows; time stamps 1.8e-7 apart), so no kernel matches it bit for bit.  The
+ * library evaluates atan2 in float64, rounds ONCE to float32 — the correctly rounded value — and then follows the
+ * reference in float32, operation by operation; the float32 quotient is widened to float64 (min maps to exactly 0, max to
+ * exactly 1, so the renormalisation inside the de-skew is the identity on it).  RANGE  within 4 x the reference's own
+ * float32-rows-against-float64-rows difference of every row (tests/test_timestamps_audit.py measures it,
+ * tests/test_gpu_timestamps.py holds the kernels to it and, bit for bit, to a numpy model of the arithmetic above).
+ * SEAM  y = +0 / -0 with x < 0 gives +pi / -pi: with phi_0 = pi, clockwise, both end at exactly 0.  A row within about
+ * 1.5e-7 rad of the seam but not on it gets 0 or 1 depending on the last bit of arctan2 — the reference's own float32 and
+ * float64 evaluations disagree there — and is outside the range above.  One row, or rows that all share one azimuth:
+ * 0 / 0 = NaN for every row, as in the reference.  A NaN coordinate is not defined here: numpy's min / max hand it on to
+ * every row, the device's fmin / fmax drop it (that row gets NaN, the others are unaffected).
+ * Refused (ICP_ERR_INVALID_ARGUMENT, with a message): n <= 0 (the reference raises on an empty scan), a stride other than
+ * 3 or 4, and a call while a registration or a frame of the context is in flight (shared scratch, as for the alignment
+ * seams).  Two launches; with device input and output the stream is never waited on. */
+int icp_estimate_timestamps(icp_ctx* ctx, const float* rows, int64_t n, int stride, int mem, int clockwise, double phi_0,
+                            double* timestamps_out, int out_mem);
+/* KITTI360Sequence.__getitem__ (slam/dataset/kitti_360_dataset.py:170-185): what the reference's KITTI-360 reader does to
+ * one raw scan — KITTIOdometrySequence.correct_scan and estimate_timestamps (there: clockwise, phi_0 = pi) — from ONE
+ * read of the scan, in the same two launches.  xyz_out [n,3] float64: the bits of icp_kitti_correct_scan; timestamps_out
+ * [n] float64: the bits of icp_estimate_timestamps (arithmetic, seam, NaN cases and refusals as stated there). */
+int icp_kitti360_prepare(icp_ctx* ctx, const float* scan, int64_t n, int stride, int mem, int clockwise, double phi_0,
+                         double* xyz_out, double* timestamps_out, int out_mem);
+
 /* ---- local map: KdTreeLocalMap (slam/odometry/local_map.py:254-427) ---------------------------------------------- */
 int icp_map_init(icp_ctx* ctx);                                             /* init()               :279-288 */
 int icp_map_set(icp_ctx* ctx, const float* xyz, int64_t m, int mem);        /* set_map_pointcloud() :289-299 */
@@ -685,6 +714,12 @@ typedef struct icp_preprocess_frame {
     int32_t* count_out;       /* required: V */
 } icp_preprocess_frame;
 int icp_batch_preprocess(icp_batch* batch, const icp_preprocess_frame* frames, double voxel_size);
+/* estimate_timestamps (slam/common/geometry.py:443-466) for every member in two launches (device memory): per member the
+ * bits of icp_estimate_timestamps — its arithmetic, seam band, all-equal-azimuth NaN and NaN-coordinate deviation hold
+ * here.  A member with n[b] == 0 or a NULL scan sits out; refused: a stride other than 3 or 4, no member with rows, members
+ * on different streams, a registration or a frame in flight on a member. */
+int icp_batch_estimate_timestamps(icp_batch* batch, const float* const* rows, const int64_t* n, int stride, int clockwise,
+                                  double phi_0, double* const* timestamps_out);
 int icp_batch_project_rows(icp_batch* batch, const float* const* xyz, const int64_t* n, float* const* vmap_out,
                            float* const* rows_out);
 int icp_batch_stage(icp_batch* batch, const float* const* xyz, const int64_t* n, int row_mode);

@@ -8,6 +8,7 @@
 
 #include <atomic>
 
+#include "frame_loop.h"
 #include "icp_internal.h"
 #include "map_move_device.h"
 
@@ -713,6 +714,62 @@ int icp_distort(icp_ctx* ctx, const float* xyz, const double* timestamps, int64_
     if ((rc = export_finish(ctx, xyz_out, odev, (size_t)n * 24, out_mem))) return rc;
     if (out_mem == ICP_MEM_HOST || mem == ICP_MEM_HOST) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ICP_OK;
+}
+
+// ---- time stamps from the azimuth ---------------------------------------------------------------------------------------
+// a frame launched on the context (by itself or by a batch) and not yet ended
+static bool frame_in_flight(const icp_ctx* ctx) {
+    return (ctx->frame && ctx->frame->launched) || (ctx->pframe && ctx->pframe->launched);
+}
+
+// What icp_estimate_timestamps / icp_kitti360_prepare refuse.  They stage into scratch a registration and a frame use (the
+// staging buffers, the scan buffers of the de-skew): refused while one is enqueued or uncollected, as the alignment seams are.
+static int timestamps_refusals(icp_ctx* ctx, const char* who, int64_t n, int stride, int mem, int out_mem) {
+    const std::string w = std::string(who) + ": ";
+    if (n <= 0 || n > INT32_MAX) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, (w + "at least one row is required (the reference raises on an empty scan)").c_str());
+    if (stride != 3 && stride != 4) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, (w + "stride is 3 (xyz rows) or 4 (x, y, z, reflectance records)").c_str());
+    if ((mem != ICP_MEM_HOST && mem != ICP_MEM_DEVICE) || (out_mem != ICP_MEM_HOST && out_mem != ICP_MEM_DEVICE))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, (w + "host or device memory").c_str());
+    if (ctx->in_registration || ctx->result_pending()) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, (w + "registration in progress").c_str());
+    if (frame_in_flight(ctx)) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, (w + "a frame is launched and awaits its end").c_str());
+    return ICP_OK;
+}
+
+static int timestamps_run(icp_ctx* ctx, const float* rows, int64_t n, int stride, int mem, int clockwise, double phi_0,
+                          double* xyz_out, double* timestamps_out, int out_mem) {
+    const void* in;
+    int rc = import_buffer(ctx, rows, (size_t)n * stride * 4, mem, ctx->stage_in, &in);
+    if (rc) return rc;
+    void *xdev, *tdev;
+    if ((rc = export_target(ctx, xyz_out, (size_t)n * 24, out_mem, ctx->stage_out, &xdev))) return rc;
+    if ((rc = export_target(ctx, timestamps_out, (size_t)n * 8, out_mem, ctx->stage_out2, &tdev))) return rc;
+    if ((rc = estimate_timestamps_device(ctx, (const float*)in, n, stride, clockwise != 0, phi_0, (double*)tdev, (double*)xdev)))
+        return rc;
+    if ((rc = export_finish(ctx, xyz_out, xdev, (size_t)n * 24, out_mem))) return rc;
+    if ((rc = export_finish(ctx, timestamps_out, tdev, (size_t)n * 8, out_mem))) return rc;
+    if (out_mem == ICP_MEM_HOST || mem == ICP_MEM_HOST) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ICP_OK;
+}
+
+int icp_estimate_timestamps(icp_ctx* ctx, const float* rows, int64_t n, int stride, int mem, int clockwise, double phi_0,
+                            double* timestamps_out, int out_mem) {
+    if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    DeviceGuard device_guard(ctx, false);  // (beside a map update on its own stream)
+    int rc = timestamps_refusals(ctx, "icp_estimate_timestamps", n, stride, mem, out_mem);
+    if (rc) return rc;
+    if (!rows || !timestamps_out) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_estimate_timestamps: rows and timestamps_out are required");
+    return timestamps_run(ctx, rows, n, stride, mem, clockwise, phi_0, nullptr, timestamps_out, out_mem);
+}
+
+int icp_kitti360_prepare(icp_ctx* ctx, const float* scan, int64_t n, int stride, int mem, int clockwise, double phi_0,
+                         double* xyz_out, double* timestamps_out, int out_mem) {
+    if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    DeviceGuard device_guard(ctx, false);  // (beside a map update on its own stream)
+    int rc = timestamps_refusals(ctx, "icp_kitti360_prepare", n, stride, mem, out_mem);
+    if (rc) return rc;
+    if (!scan || !xyz_out || !timestamps_out)
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_kitti360_prepare: scan, xyz_out and timestamps_out are required");
+    return timestamps_run(ctx, scan, n, stride, mem, clockwise, phi_0, xyz_out, timestamps_out, out_mem);
 }
 
 // ---- local map ------------------------------------------------------------------------------------------------------
@@ -2391,6 +2448,38 @@ int icp_batch_preprocess(icp_batch* b, const icp_preprocess_frame* frames, doubl
         for (icp_ctx* ctx : b->members)
             if (!ctx->error.empty()) return batch_fail(b, rc, ctx->error);
         return batch_fail(b, rc, "batched preprocessing: HIP error");
+    }
+    return ICP_OK;
+}
+
+// estimate_timestamps (slam/common/geometry.py:443-466) for every member in two launches
+int icp_batch_estimate_timestamps(icp_batch* b, const float* const* rows, const int64_t* n, int stride, int clockwise,
+                                  double phi_0, double* const* timestamps_out) {
+    if (!b) return ICP_ERR_INVALID_ARGUMENT;
+    if (!rows || !n || !timestamps_out)
+        return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched time stamps: rows[], n[] and timestamps_out[] are required");
+    if (stride != 3 && stride != 4)
+        return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched time stamps: stride is 3 (xyz rows) or 4 (x, y, z, reflectance records)");
+    DeviceGuard device_guard(b->device);
+    const int count = (int)b->members.size();
+    bool any = false;
+    for (int i = 0; i < count; ++i) {
+        const std::string who = "batched time stamps, member " + std::to_string(i) + ": ";
+        if (n[i] < 0 || n[i] > INT32_MAX) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "invalid row count");
+        if (n[i] == 0 || !rows[i]) continue;  // sits out
+        if (!timestamps_out[i]) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "timestamps_out is required");
+        icp_ctx* ctx = b->members[i];
+        if (ctx->result_pending()) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "registration in progress");
+        if (frame_in_flight(ctx)) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "a frame is launched and awaits its end");
+        any = true;
+    }
+    if (!any) return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched time stamps: every member sits out (n <= 0)");
+    int rc = front_batch_check(b, "batched time stamps", false);
+    if (rc || (rc = front_batch_flush(b))) return rc;
+    if ((rc = estimate_timestamps_batch_device(b->members.data(), count, rows, n, stride, clockwise != 0, phi_0, timestamps_out))) {
+        for (icp_ctx* ctx : b->members)
+            if (!ctx->error.empty()) return batch_fail(b, rc, ctx->error);
+        return batch_fail(b, rc, "batched time stamps: HIP error");
     }
     return ICP_OK;
 }

@@ -852,7 +852,7 @@ __global__ void k_distort(const float* __restrict__ xyz, const double* __restric
     distort_body(xyz, ts, n, part, nparts, a, out);
 }
 
-static constexpr int DISTORT_PARTS = 64;  // workgroups of the timestamp min / max
+// (DISTORT_PARTS, the workgroups of the timestamp min / max: icp_internal.h)
 
 // Axis and angle of the rotation the reference de-skews by: scipy's Rotation.from_matrix of the 3x3 block handed over, as
 // Slerp then scales it.  An exact rotation goes straight to the quaternion; a matrix that is not one — the frame loop's

@@ -769,6 +769,18 @@ int compact_valid_rows_batch(icp_ctx* const* ctxs, int count, const float* const
                              float* const* out, int* const* count_host_mapped);
 int kitti_correct_device(icp_ctx* ctx, const float* scan_dev, int64_t n, int stride, double* out_dev);
 
+// ---- timestamps.hip
+// workgroups (of 256) of a min / max reduction over a frame's rows: the time stamps of the de-skew (grid_sample.hip) and the
+// azimuths they are estimated from (timestamps.hip); the partials live in ctx->scan_b
+static constexpr int DISTORT_PARTS = 64;
+// estimate_timestamps (slam/common/geometry.py:443-466) of [n, stride] float32 rows in two launches; xyz_out_dev (may be
+// NULL): the rows corrected by KITTIOdometrySequence.correct_scan as well, from the same load (icp_kitti360_prepare)
+int estimate_timestamps_device(icp_ctx* ctx, const float* rows_dev, int64_t n, int stride, bool clockwise, double phi_0,
+                               double* ts_dev, double* xyz_out_dev);
+// ... of `count` scans in two launches on ctxs[0]'s stream (a member with n[b] <= 0 or a NULL scan sits out)
+int estimate_timestamps_batch_device(icp_ctx* const* ctxs, int count, const float* const* rows_dev, const int64_t* n,
+                                     int stride, bool clockwise, double phi_0, double* const* ts_dev);
+
 // ---- projective.hip
 int normal_map_device(icp_ctx* ctx, const float* vmap_dev, int ks, float* nmap_dev);
 int neighbors_device(icp_ctx* ctx, const float* tgt, const float* ref, const float* fld, int k_maps, int c_fld,

@@ -155,21 +155,7 @@ __global__ void k_kitti_correct(const float* __restrict__ scan, int n, int strid
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float x = scan[(size_t)i * stride], y = scan[(size_t)i * stride + 1], z = scan[(size_t)i * stride + 2];
-    // axes = cross(xyz, [0,0,1]) = (y, -x, 0), normalised in float32 (:209-211)
-    const float nrm = sqrtf(__fadd_rn(__fmul_rn(y, y), __fmul_rn(x, x)));
-    const float ax = y / nrm, ay = -x / nrm;  // az = 0 (0/nrm; NaN only when x = y = 0, as in the reference)
-    const float az = 0.0f / nrm;
-    const double theta = 0.205 * 3.14159265358979323846 / 180.0;
-    const double c = cos(theta), s = sin(theta);
-    // rotations = c * eye + s * u_cross + (1 - c) * u_outer   (:216-228), row i of R times xyz
-    const double o00 = (double)__fmul_rn(ax, ax), o01 = (double)__fmul_rn(ax, ay), o02 = (double)__fmul_rn(ax, az);
-    const double o11 = (double)__fmul_rn(ay, ay), o12 = (double)__fmul_rn(ay, az), o22 = (double)__fmul_rn(az, az);
-    const double r00 = c + (1 - c) * o00, r01 = s * (double)(-az) + (1 - c) * o01, r02 = s * (double)ay + (1 - c) * o02;
-    const double r10 = s * (double)az + (1 - c) * o01, r11 = c + (1 - c) * o11, r12 = s * (double)(-ax) + (1 - c) * o12;
-    const double r20 = s * (double)(-ay) + (1 - c) * o02, r21 = s * (double)ax + (1 - c) * o12, r22 = c + (1 - c) * o22;
-    out[3 * (size_t)i] = r00 * x + r01 * y + r02 * z;
-    out[3 * (size_t)i + 1] = r10 * x + r11 * y + r12 * z;
-    out[3 * (size_t)i + 2] = r20 * x + r21 * y + r22 * z;
+    kitti_correct_row(x, y, z, out + 3 * (size_t)i);  // (projection_device.h: shared with the raw-scan kernel of timestamps.hip)
 }
 
 int kitti_correct_device(icp_ctx* ctx, const float* scan_dev, int64_t n, int stride, double* out_dev) {

@@ -45,4 +45,25 @@ __device__ inline void spherical_rowcol_for_rounding(float x, float y, float z, 
     if (near_half(row) || near_half(col)) spherical_rowcol(x, y, z, r, fov_down_abs, fov, height, width, true, row, col);
 }
 
+// One row of `KITTIOdometrySequence.correct_scan` (slam/dataset/kitti_dataset.py:202-231): the body of k_kitti_correct
+// (projection.hip) and of the raw-scan form of k_azimuth (timestamps.hip), which corrects the row it has just loaded —
+// one function, so both write the same bits.  out: the row's three float64 coordinates.
+__device__ __forceinline__ void kitti_correct_row(float x, float y, float z, double* __restrict__ out) {
+    // axes = cross(xyz, [0,0,1]) = (y, -x, 0), normalised in float32 (:209-211)
+    const float nrm = sqrtf(__fadd_rn(__fmul_rn(y, y), __fmul_rn(x, x)));
+    const float ax = y / nrm, ay = -x / nrm;  // az = 0 (0/nrm; NaN only when x = y = 0, as in the reference)
+    const float az = 0.0f / nrm;
+    const double theta = 0.205 * 3.14159265358979323846 / 180.0;
+    const double c = cos(theta), s = sin(theta);
+    // rotations = c * eye + s * u_cross + (1 - c) * u_outer   (:216-228), row i of R times xyz
+    const double o00 = (double)__fmul_rn(ax, ax), o01 = (double)__fmul_rn(ax, ay), o02 = (double)__fmul_rn(ax, az);
+    const double o11 = (double)__fmul_rn(ay, ay), o12 = (double)__fmul_rn(ay, az), o22 = (double)__fmul_rn(az, az);
+    const double r00 = c + (1 - c) * o00, r01 = s * (double)(-az) + (1 - c) * o01, r02 = s * (double)ay + (1 - c) * o02;
+    const double r10 = s * (double)az + (1 - c) * o01, r11 = c + (1 - c) * o11, r12 = s * (double)(-ax) + (1 - c) * o12;
+    const double r20 = s * (double)(-ay) + (1 - c) * o02, r21 = s * (double)ax + (1 - c) * o12, r22 = c + (1 - c) * o22;
+    out[0] = r00 * x + r01 * y + r02 * z;
+    out[1] = r10 * x + r11 * y + r12 * z;
+    out[2] = r20 * x + r21 * y + r22 * z;
+}
+
 }  // namespace icp

@@ -122,6 +122,8 @@ EXPORTED_SYMBOLS = {
     "icp_grid_sample_padded": (_INT, [_P, _P, _I64, C.c_double, _P, _P, _P]),
     "icp_grid_sample_padded_f64": (_INT, [_P, _P, _I64, C.c_double, _P, _P, _P]),
     "icp_distort": (_INT, [_P, _P, _P, _I64, _INT, _P, _P, _INT]),
+    "icp_estimate_timestamps": (_INT, [_P, _P, _I64, _INT, _INT, _INT, C.c_double, _P, _INT]),
+    "icp_kitti360_prepare": (_INT, [_P, _P, _I64, _INT, _INT, _INT, C.c_double, _P, _P, _INT]),
     "icp_map_init": (_INT, [_P]),
     "icp_map_set": (_INT, [_P, _P, _I64, _INT]),
     "icp_map_update": (_INT, [_P, _P, _P, _I64, _INT, _INT, C.POINTER(_I64)]),
@@ -178,6 +180,7 @@ EXPORTED_SYMBOLS = {
     "icp_batch_pmap_update": (_INT, [_P, _P, _P, _INT, _INT]),
     "icp_batch_register_end": (_INT, [_P, _P, _P, _P]),
     "icp_batch_preprocess": (_INT, [_P, C.POINTER(IcpPreprocessFrame), C.c_double]),
+    "icp_batch_estimate_timestamps": (_INT, [_P, _P, _P, _INT, _INT, C.c_double, _P]),
     "icp_batch_project_rows": (_INT, [_P, _P, _P, _P, _P]),
     "icp_batch_stage": (_INT, [_P, _P, _P, _INT]),
     "icp_batch_odometry_init": (_INT, [_P, C.POINTER(IcpFrameConfig)]),

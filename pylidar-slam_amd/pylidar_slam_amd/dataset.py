@@ -1,6 +1,7 @@
 """Dataset side of the hot path: the `DatasetLoader` plugin surface, a synthetic-scan loader for
-BASELINE.json's synthetic configurations, and the KITTI odometry reader with the scan correction and the spherical
-projection done on the MI355X.
+BASELINE.json's synthetic configurations, the KITTI odometry reader with the scan correction and the spherical
+projection done on the MI355X, and the KITTI-360 reader of RAW (un-rectified) scans: correction and azimuth time stamps
+from one upload, so that `Distortion` has something to de-skew by.
 
   reference                                                             here
   DatasetLoader            slam/dataset/configuration.py:31-119         DatasetLoader
@@ -8,6 +9,9 @@ projection done on the MI355X.
   KITTIDatasetLoader       slam/dataset/kitti_dataset.py:311-400        KITTIDatasetLoader
   read_ground_truth_file / read_calib_file   kitti_dataset.py:40-91     same names
   (none: the reference ships no synthetic data)                         SyntheticSequence / SyntheticDatasetLoader
+  get_sequence_poses       slam/dataset/kitti_360_dataset.py:61-96      kitti360_sequence_poses (numpy + scipy, no pandas)
+  KITTI360Sequence         slam/dataset/kitti_360_dataset.py:99-185     KITTI360Sequence (one `kitti360_prepare` per item)
+  KITTI360DatasetLoader    slam/dataset/kitti_360_dataset.py:214-277    KITTI360DatasetLoader
 
 Items are the reference's data_dict: `numpy_pc` [N,3] float32 (host), `vertex_map` [3,H,W] float32 (device tensor),
 `absolute_pose_gt` [4,4].  The GPU context lives in the main process: use these datasets with num_workers = 0.
@@ -28,7 +32,8 @@ from .synthetic import SceneConfig, ray_directions, render_scan, trajectory
 
 __all__ = ["DatasetLoader", "SyntheticDatasetConfig", "SyntheticSequence", "SyntheticDatasetLoader", "KITTIConfig",
            "KITTIOdometrySequence", "KITTIDatasetLoader", "read_ground_truth_file", "read_calib_file",
-           "kitti_read_scan", "compute_relative_poses"]
+           "kitti_read_scan", "compute_relative_poses", "KITTI360Config", "KITTI360Sequence", "KITTI360DatasetLoader",
+           "kitti360_sequence_poses", "kitti360_drive_foldername", "KITTI360_DRIVES"]
 
 
 def compute_relative_poses(absolute: np.ndarray) -> np.ndarray:
@@ -283,6 +288,168 @@ class KITTIDatasetLoader(DatasetLoader):
             return [KITTIOdometrySequence(str(self.odometry_sequence_dir), s, self._ctx, c.lidar_key, c.absolute_gt_key,
                                           with_numpy_pc=c.with_numpy_pc, device_items=c.device_items)
                     for s in present], present
+
+        tr, ev, te = get(c.train_sequences), get(c.eval_sequences), get(c.test_sequences)
+        return tr or (None, None), ev or (None, None), te or (None, None), lambda x: x
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# KITTI-360 (http://www.cvlibs.net/datasets/kitti-360/): raw HDL-64 scans, not motion-compensated — the one dataset of the
+# reference that reaches its `Distortion` filter, through azimuth time stamps (slam/dataset/kitti_360_dataset.py:170-185)
+KITTI360_DRIVES = {0: 11518, 2: 19240, 3: 1031, 4: 11587, 5: 6743, 6: 9699, 7: 3396, 9: 14056, 10: 3836}  # drive id: frames
+
+# calib_cam_to_pose.txt (image_00) and calib_cam_to_velo.txt of the dataset's calibration folder
+_KITTI360_CAM0_TO_POSE = np.array([[0.0371783278, -0.0986182135, 0.9944306009, 1.5752681039],
+                                   [0.9992675562, -0.0053553387, -0.0378902567, 0.0043914093],
+                                   [0.0090621821, 0.9951109327, 0.0983468786, -0.6500000000],
+                                   [0.0, 0.0, 0.0, 1.0]], dtype=np.float64)
+_KITTI360_CAM0_TO_VELO = np.array([[0.04307104361, -0.08829286498, 0.995162929, 0.8043914418],
+                                   [-0.999004371, 0.007784614041, 0.04392796942, 0.2993489574],
+                                   [-0.01162548558, -0.9960641394, -0.08786966659, -0.1770225824],
+                                   [0.0, 0.0, 0.0, 1.0]], dtype=np.float64)
+
+
+def kitti360_drive_foldername(drive_id: int) -> str:
+    return f"2013_05_28_drive_{int(drive_id):04}_sync"
+
+
+def _kitti360_velodyne_path(root_dir, drive_id: int) -> Path:
+    return Path(root_dir) / "data_3d_raw" / kitti360_drive_foldername(drive_id) / "velodyne_points"
+
+
+def kitti360_sequence_poses(root_dir, drive_id: int) -> Optional[np.ndarray]:
+    """`get_sequence_poses` (kitti_360_dataset.py:61-96) on the host, without pandas: one lidar pose [F,4,4] float64 per
+    frame, or None without a `data_poses/<drive>/poses.txt`.  The ground truth holds fewer poses than frames (rows `frame
+    index, 12 pose entries`): rotations are interpolated by scipy's Slerp and translations linearly at the frame instants
+    of `timestamps.txt` (nanoseconds; clipped to the first / last key instant), then taken to the lidar frame."""
+    from scipy.interpolate import interp1d
+    from scipy.spatial.transform import Rotation, Slerp
+
+    assert_debug(int(drive_id) in KITTI360_DRIVES, f"KITTI-360 has no drive {drive_id}")
+    gt_file = Path(root_dir) / "data_poses" / kitti360_drive_foldername(drive_id) / "poses.txt"
+    if not gt_file.exists():
+        return None
+    rows = np.loadtxt(str(gt_file), dtype=np.float64, ndmin=2)  # [K, 13]
+    key_frames = rows[:, 0].astype(np.int32)
+    k = rows.shape[0]
+    key_poses = np.concatenate((rows[:, 1:], np.zeros((k, 3)), np.ones((k, 1))), axis=1).reshape(k, 4, 4)
+    with open(_kitti360_velodyne_path(root_dir, drive_id) / "timestamps.txt", "r") as f:
+        stamps = [line.strip() for line in f if line.strip()]
+    instants = np.array(stamps, dtype="datetime64[ns]").astype(np.int64).astype(np.float64)
+    key_instants = instants[key_frames]
+    instants = instants.clip(min=key_instants.min(), max=key_instants.max())
+    poses = np.zeros((instants.shape[0], 4, 4), dtype=np.float64)
+    poses[:, :3, :3] = Slerp(key_instants, Rotation.from_matrix(key_poses[:, :3, :3]))(instants).as_matrix()
+    poses[:, :3, 3] = interp1d(key_instants, key_poses[:, :3, 3], axis=0)(instants)
+    poses[:, 3, 3] = 1.0
+    velo_to_pose = _KITTI360_CAM0_TO_POSE.dot(np.linalg.inv(_KITTI360_CAM0_TO_VELO))
+    return np.einsum("nij,jk->nik", poses, velo_to_pose)
+
+
+def _kitti360_from_first(poses: np.ndarray) -> np.ndarray:
+    return np.einsum("ij,njk->nik", np.linalg.inv(poses[0]), poses)  # :133, :240
+
+
+@dataclass
+class KITTI360Config:
+    """kitti_360_dataset.py:189-205."""
+    root_dir: str = ""
+    dataset: str = "kitti_360"
+    lidar_height: int = 64
+    lidar_width: int = 1024
+    up_fov: float = 3.0
+    down_fov: float = -24.0
+    train_sequences: List[int] = field(default_factory=lambda: [0, 2, 3, 4, 5, 6, 7, 9, 10])
+    test_sequences: List[int] = field(default_factory=lambda: [0, 2, 3, 4, 5, 6, 7])
+    eval_sequences: List[int] = field(default_factory=lambda: [9, 10])
+    device: str = "cuda:0"       # the GPU scans are corrected and timed on
+    # False: `numpy_pc` / `numpy_pc_timestamps` are host arrays, as in the reference; True: both stay cuda tensors, so
+    # `distortion_mi355x` -> `grid_sample_mi355x` -> the frame calls run without a round trip (see SyntheticDatasetConfig)
+    device_items: bool = False
+
+
+class KITTI360Sequence(Dataset):
+    """kitti_360_dataset.py:99-185: the raw .bin is read on the host, then ONE `IcpContext.kitti360_prepare` corrects the
+    scan and estimates its time stamps (clockwise, phi_0 = pi) — nothing is computed per point on the host.  `ctx`: an
+    IcpContext, or a callable returning one (created when the first item is read)."""
+
+    def __init__(self, kitti360_root_dir: str, drive_id: int, ctx, device_items: bool = False):
+        self.root_dir = Path(kitti360_root_dir)
+        self.drive_id = int(drive_id)
+        assert_debug(self.drive_id in KITTI360_DRIVES, f"KITTI-360 has no drive {drive_id}")
+        self.lidar_path = _kitti360_velodyne_path(self.root_dir, self.drive_id) / "data"
+        assert_debug(self.lidar_path.exists(), f"The drive directory {self.lidar_path} does not exist")
+        self.size = KITTI360_DRIVES[self.drive_id]
+        self._ctx = ctx
+        self._device_items = device_items
+        self.gt_poses = kitti360_sequence_poses(self.root_dir, self.drive_id)
+        if self.gt_poses is not None:
+            self.gt_poses = _kitti360_from_first(self.gt_poses)
+
+    @property
+    def ctx(self) -> IcpContext:
+        if not isinstance(self._ctx, IcpContext):
+            self._ctx = self._ctx()
+        return self._ctx
+
+    def __len__(self):
+        return self.size
+
+    def __getitem__(self, idx) -> dict:
+        assert_debug(0 <= idx < self.size)
+        scan_path = self.lidar_path / f"{idx:010}.bin"
+        assert_debug(scan_path.exists() and scan_path.is_file(), f"The file {scan_path} does not exist")
+        scan = kitti_read_scan(str(scan_path))
+        ctx = self.ctx
+        d = {}
+        if self._device_items:
+            xyz, ts = ctx.kitti360_prepare(torch.from_numpy(scan).to(ctx.device))
+            d["numpy_pc"] = xyz.to(torch.float32)  # rounded once, as KITTIOdometrySequence.correct_scan does
+        else:
+            xyz, ts = ctx.kitti360_prepare(scan)
+            d["numpy_pc"] = xyz.astype(np.float32)
+        d["numpy_reflectance"] = scan[:, 3:]
+        d["numpy_pc_timestamps"] = ts
+        if self.gt_poses is not None:
+            d[DatasetLoader.absolute_gt_key()] = self.gt_poses[idx]
+        return d
+
+
+class KITTI360DatasetLoader(DatasetLoader):
+    """kitti_360_dataset.py:214-277.  The GPU context is created with the first item read, so ground truth, projector and
+    the sequence lists are available without a device."""
+
+    def __init__(self, config: KITTI360Config):
+        super().__init__(config)
+        self.root_dir = Path(config.root_dir)
+        assert_debug(self.root_dir.exists())
+        self._context = None
+
+    def _ctx(self) -> IcpContext:
+        if self._context is None:
+            c = self.config
+            self._context = IcpContext(height=c.lidar_height, width=c.lidar_width, up_fov=c.up_fov, down_fov=c.down_fov,
+                                       device=_device_index(c.device))
+        return self._context
+
+    def projector(self) -> SphericalProjector:
+        c = self.config
+        return SphericalProjector(c.lidar_height, c.lidar_width, 3, c.up_fov, c.down_fov)
+
+    def get_ground_truth(self, drive_id):  # :236-241
+        poses = kitti360_sequence_poses(self.root_dir, int(drive_id))
+        if poses is None:
+            return None
+        return _eval.compute_relative_poses(_kitti360_from_first(poses))  # the reference's own convention: rel[0] = abs[0]
+
+    def sequences(self):  # :243-277 (drives whose scans are absent are left out, as KITTIDatasetLoader does)
+        c = self.config
+
+        def get(drives):
+            if not drives:
+                return None
+            present = [str(d) for d in drives if (_kitti360_velodyne_path(self.root_dir, int(d)) / "data").exists()]
+            return [KITTI360Sequence(str(self.root_dir), int(d), self._ctx, c.device_items) for d in present], present
 
         tr, ev, te = get(c.train_sequences), get(c.eval_sequences), get(c.test_sequences)
         return tr or (None, None), ev or (None, None), te or (None, None), lambda x: x

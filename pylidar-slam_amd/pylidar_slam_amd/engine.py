@@ -351,6 +351,56 @@ class IcpContext:
                                           pose.ctypes.data, out.ctypes.data, MEM_HOST))
         return out
 
+    # ---- time stamps from the azimuth --------------------------------------------------------------------------------
+    @staticmethod
+    def _scan_rows(rows, what: str):
+        """[N, 3] or [N, 4] float32 contiguous rows, numpy or cuda tensor (another dtype / layout is converted here)."""
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            a = rows if (rows.dtype == torch.float32 and rows.is_contiguous()) else rows.to(torch.float32).contiguous()
+        else:
+            a = np.ascontiguousarray(rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else rows,
+                                     dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] not in (3, 4):
+            raise AssertionError(f"{what}: expected [N, 3] or [N, 4] rows, got {tuple(a.shape)}")
+        return a
+
+    def estimate_timestamps(self, rows: Array, clockwise: bool = True, phi_0: float = 0.0):
+        """`estimate_timestamps` (slam/common/geometry.py:443-466): [N, 3] (or the [N, 4] records of a .bin scan) float32
+        rows -> [N] float64 time stamps in [0, 1] from the azimuth.  numpy in -> numpy out; a cuda tensor in -> a cuda
+        tensor out on torch's current stream, without a synchronisation: what `frame_launch(timestamps=...)`, `distort`
+        and `IcpBatch.preprocess` take.  Arithmetic, seam and NaN cases: `icp_estimate_timestamps`, include/icp_mi355x.h."""
+        self._bind(rows)
+        a = self._scan_rows(rows, "estimate_timestamps")
+        n, stride = int(a.shape[0]), int(a.shape[1])
+        if isinstance(a, torch.Tensor):
+            out = torch.empty(n, dtype=torch.float64, device=a.device)
+            self._check(self._lib.icp_estimate_timestamps(self._h, a.data_ptr() if n else None, n, stride, MEM_DEVICE,
+                                                          int(bool(clockwise)), float(phi_0), out.data_ptr(), MEM_DEVICE))
+            return out
+        out = np.empty(n, np.float64)
+        self._check(self._lib.icp_estimate_timestamps(self._h, a.ctypes.data, n, stride, MEM_HOST, int(bool(clockwise)),
+                                                      float(phi_0), out.ctypes.data, MEM_HOST))
+        return out
+
+    def kitti360_prepare(self, scan: Array, clockwise: bool = True, phi_0: float = np.pi):
+        """`KITTI360Sequence.__getitem__` (slam/dataset/kitti_360_dataset.py:170-185) for one raw scan, from one upload and
+        one read of it: (xyz [N, 3] float64 — the bits of `kitti_correct_scan` —, time stamps [N] float64 — the bits of
+        `estimate_timestamps(scan, clockwise, phi_0)`).  numpy in -> numpy out, cuda tensor in -> cuda tensors out."""
+        self._bind(scan)
+        a = self._scan_rows(scan, "kitti360_prepare")
+        n, stride = int(a.shape[0]), int(a.shape[1])
+        if isinstance(a, torch.Tensor):
+            xyz = torch.empty((n, 3), dtype=torch.float64, device=a.device)
+            ts = torch.empty(n, dtype=torch.float64, device=a.device)
+            self._check(self._lib.icp_kitti360_prepare(self._h, a.data_ptr() if n else None, n, stride, MEM_DEVICE,
+                                                       int(bool(clockwise)), float(phi_0), xyz.data_ptr(), ts.data_ptr(),
+                                                       MEM_DEVICE))
+            return xyz, ts
+        xyz, ts = np.empty((n, 3), np.float64), np.empty(n, np.float64)
+        self._check(self._lib.icp_kitti360_prepare(self._h, a.ctypes.data, n, stride, MEM_HOST, int(bool(clockwise)),
+                                                   float(phi_0), xyz.ctypes.data, ts.ctypes.data, MEM_HOST))
+        return xyz, ts
+
     # ---- local map ---------------------------------------------------------------------------------------------------
     def map_init(self):
         self._check(self._lib.icp_map_init(self._h))
@@ -1104,6 +1154,35 @@ class IcpBatch:
         if t.ndim != 2 or t.shape[1] != 3:
             raise AssertionError(f"{what}: expected [n, 3] rows, got {tuple(t.shape)}")
         return t
+
+    def estimate_timestamps(self, rows_b, clockwise: bool = True, phi_0: float = 0.0):
+        """`IcpContext.estimate_timestamps(rows_b[b], clockwise, phi_0)` for every member in two launches
+        (icp_batch_estimate_timestamps): a list of [n_b] float64 cuda tensors.  rows_b[b]: [n_b, 3] or [n_b, 4] float32
+        cuda rows, all of one width; None or an empty tensor: the member sits out (None in the result)."""
+        b = len(self.contexts)
+        if len(rows_b) != b:
+            raise AssertionError(f"expected {b} scans, got {len(rows_b)}")
+        keep = []
+        for k, a in enumerate(rows_b):
+            if a is None:
+                keep.append(None)
+                continue
+            if not (isinstance(a, torch.Tensor) and a.is_cuda):
+                raise AssertionError(f"batched time stamps, member {k}: the rows must be a cuda tensor (device pointers)")
+            keep.append(IcpContext._scan_rows(a, f"batched time stamps, member {k}"))
+        widths = {int(k.shape[1]) for k in keep if k is not None}
+        if len(widths) > 1:
+            raise AssertionError("batched time stamps: the members' rows must share one width (3 or 4)")
+        stride = widths.pop() if widths else 3
+        out = [torch.empty(int(k.shape[0]), dtype=torch.float64, device=k.device)
+               if k is not None and k.shape[0] else None for k in keep]
+        self.use_torch_stream()
+        rows = (C.c_void_p * b)(*[k.data_ptr() if o is not None else None for k, o in zip(keep, out)])
+        n = (C.c_int64 * b)(*[int(k.shape[0]) if o is not None else 0 for k, o in zip(keep, out)])
+        ts = (C.c_void_p * b)(*[o.data_ptr() if o is not None else None for o in out])
+        self._keep_timestamped = keep  # (read by the enqueued launches)
+        self._check(self._lib.icp_batch_estimate_timestamps(self._h, rows, n, stride, int(bool(clockwise)), float(phi_0), ts))
+        return out
 
     def project_rows(self, scans, rows=True):
         """`IcpContext.project_rows(scans[b])` for every member in two launches (icp_batch_project_rows): a list of

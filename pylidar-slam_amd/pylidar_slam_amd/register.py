@@ -14,7 +14,7 @@ import sys
 from enum import Enum
 
 ALGORITHM_NAME = "icp_F2M_mi355x"
-DATASET_NAMES = ("synthetic_mi355x", "kitti_mi355x")
+DATASET_NAMES = ("synthetic_mi355x", "kitti_mi355x", "kitti_360_mi355x")
 FILTER_NAMES = ("grid_sample_mi355x", "distortion_mi355x", "voxelization_mi355x", "to_device_mi355x", "to_tensor_mi355x")
 LOCAL_MAP_NAMES = ("hashgrid_local_map_mi355x", "projective_local_map_mi355x")
 ALIGNMENT_NAMES = ("point_to_plane_gauss_newton_mi355x", "point_to_point_gauss_newton_mi355x")
@@ -38,7 +38,7 @@ def _swap_enum(owner, attr: str, extra: dict, mixins: tuple, namespace: dict):
 
 def register_with_reference():
     """Call once, before `SLAM.init()` / `run.py`'s hydra main builds the pipeline. Returns the patched ODOMETRY enum
-    (`icp_F2M_mi355x`); DATASET gains `synthetic_mi355x` / `kitti_mi355x`, FILTER gains `grid_sample_mi355x` /
+    (`icp_F2M_mi355x`); DATASET gains `synthetic_mi355x` / `kitti_mi355x` / `kitti_360_mi355x`, FILTER gains `grid_sample_mi355x` /
     `distortion_mi355x` / `voxelization_mi355x` / `to_device_mi355x` / `to_tensor_mi355x`, LOCAL_MAP gains
     `hashgrid_local_map_mi355x` / `projective_local_map_mi355x` and RIGID_ALIGNMENT gains
     `point_to_plane_gauss_newton_mi355x` / `point_to_point_gauss_newton_mi355x` (so the reference's OWN
@@ -48,7 +48,8 @@ def register_with_reference():
     import slam.preprocessing as ref_pre
     from slam.common.utils import ObjectLoaderEnum
 
-    from .dataset import KITTIConfig, KITTIDatasetLoader, SyntheticDatasetConfig, SyntheticDatasetLoader
+    from .dataset import (KITTI360Config, KITTI360DatasetLoader, KITTIConfig, KITTIDatasetLoader, SyntheticDatasetConfig,
+                          SyntheticDatasetLoader)
     import slam.odometry.alignment as ref_alignment
     import slam.odometry.local_map as ref_local_map
     from .odometry import (Distortion, DistortionConfig, GridSample, GridSampleConfig, HashGridLocalMap,
@@ -60,7 +61,8 @@ def register_with_reference():
     odometry = _swap_enum(ref_odometry, "ODOMETRY", {ALGORITHM_NAME: (MI355XICPFrameToModel, MI355XICPConfig)},
                           (ObjectLoaderEnum,), {"type_name": classmethod(lambda cls: "algorithm")})
     _swap_enum(ref_dataset, "DATASET", {DATASET_NAMES[0]: (SyntheticDatasetLoader, SyntheticDatasetConfig),
-                                         DATASET_NAMES[1]: (KITTIDatasetLoader, KITTIConfig)},
+                                         DATASET_NAMES[1]: (KITTIDatasetLoader, KITTIConfig),
+                                         DATASET_NAMES[2]: (KITTI360DatasetLoader, KITTI360Config)},
                (ObjectLoaderEnum,), {"type_name": classmethod(lambda cls: "dataset")})
 
     def _load_filter(config, **kwargs):  # slam/preprocessing.py:243-252, against the patched enum
@@ -89,6 +91,7 @@ def register_with_reference():
         cs.store(name="icp_odometry_mi355x", group="slam/odometry", node=MI355XICPConfig)
         cs.store(name=DATASET_NAMES[0], group="dataset", node=SyntheticDatasetConfig)
         cs.store(name=DATASET_NAMES[1], group="dataset", node=KITTIConfig)
+        cs.store(name=DATASET_NAMES[2], group="dataset", node=KITTI360Config)
         cs.store(name="hashgrid_mi355x", group="slam/odometry/local_map", node=HashGridLocalMapConfig)
         cs.store(name="projective_mi355x", group="slam/odometry/local_map", node=ProjectiveLocalMapConfig)
         cs.store(name="point_to_plane_GN_mi355x", group="slam/odometry/alignment", node=PointToPlaneAlignmentConfig)
