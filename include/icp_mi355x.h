@@ -388,6 +388,28 @@ int icp_map_get(icp_ctx* ctx, float* xyz_out, int out_mem); /* current map [M,3]
  * lazily estimated normal of every hit.  Outputs [n,3], [n,3], [n] (any may be NULL). */
 int icp_nearest_neighbor_search(icp_ctx* ctx, const float* xyz, int64_t n, int mem, float* neighbor_points_out,
                                 float* neighbor_normals_out, int32_t* neighbor_index_out, int out_mem);
+/* KDTree(map).query(xyz, k) — pykdtree.kdtree.KDTree as the reference builds and queries it (slam/odometry/local_map.py:369,
+ * 385, 405) — against the kd-tree style map of the context (icp_map_set / icp_map_update*): the exact k nearest map points
+ * of n ARBITRARY query rows xyz [n,3], no distance cap.
+ *   order      ascending by (d2, original map index): exact distance ties go to the lower index.  d2 is float32,
+ *              fma(dz,dz, fma(dy,dy, dx*dx)) of the float32 coordinate differences.
+ *   outputs    dist_out [n,k] float32: sqrtf(d2), or d2 itself under ICP_KNN_SQR_DISTS; index_out [n,k] int32: indices into
+ *              the map in the insertion order icp_map_get returns.  Either may be NULL, not both.
+ *   missing    when fewer than k neighbours exist (the map holds fewer than k points, or the bound below leaves fewer) the
+ *              remaining entries are dist = +inf, index = icp_map_size() — scipy's and pykdtree's convention.  A query row
+ *              with a NaN or infinite coordinate has no neighbours: k missing entries.
+ *   bound      distance_upper_bound = b > 0 keeps only neighbours with d2 < b*b (float32 product), strictly: a point exactly
+ *              at the bound is excluded, as scipy.spatial.cKDTree does.  b <= 0 or +inf: no bound.
+ *   k          1..32.  The search options ("cell_size", max_rings, "knn_rings") never change a result.
+ * ICP_ERR_EMPTY_MAP on an empty map; ICP_ERR_INVALID_ARGUMENT (icp_last_error says why) for k outside 1..32, n < 0, both
+ * outputs NULL, unknown flags, or a registration or frame that is in flight or uncollected.  Iterations a chunked launch
+ * still holds back are enqueued first.  The call reads the grid only: normals, the nearest-neighbour cache, the
+ * registration state and the staged buffers of a frame are left as they were (it stages through buffers of its own).
+ * n = 0 returns ICP_OK and writes nothing.  Not available: a batched form, radius / ball queries, k > 32. */
+#define ICP_KNN_SQR_DISTS 1
+int icp_knn_query(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int32_t k,
+                  float distance_upper_bound /* <= 0 or +inf: none */, int32_t flags,
+                  float* dist_out, int32_t* index_out /* either may be NULL */, int out_mem);
 /* Test support for the search schedule (no reference counterpart; the reference recomputes every neighbour in every
  * iteration, slam/odometry/icp_odometry.py:274-297): the ORIGINAL map index of the point each target of the last
  * registration was matched with in its LAST iteration (-1: masked row), read back from the exact nearest-neighbour cache

@@ -10,6 +10,7 @@
 
 #include "frame_loop.h"
 #include "icp_internal.h"
+#include "knn_plan.h"
 #include "map_move_device.h"
 
 using namespace icp;
@@ -342,6 +343,7 @@ void icp_destroy(icp_ctx* ctx) {
                             &ctx->pm_n,       &ctx->pm_mv,      &ctx->pm_mn,      &ctx->pm_z,      &ctx->pm_tmp,
                             &ctx->vox_out,    &ctx->seed_orig,  &ctx->scan_desc,  &ctx->posebox,   &ctx->pose_hist_buf,
                             &ctx->hood,       &ctx->normals_carry, &ctx->tail_rows, &ctx->normals_tail, &ctx->nn_rec,
+                            &ctx->knn_in,     &ctx->knn_dist,   &ctx->knn_idx,
                             &ctx->cell_list[0][0], &ctx->cell_list[0][1], &ctx->cell_list[1][0], &ctx->cell_list[1][1], &ctx->cell_counts};
     for (DeviceBuffer* b : bufs) b->release();
     for (auto& r : ctx->rslot) {
@@ -1101,6 +1103,39 @@ int icp_nearest_neighbor_search(icp_ctx* ctx, const float* xyz, int64_t n, int m
     if ((rc = export_finish(ctx, neighbor_points_out, pdev, (size_t)n * 12, out_mem))) return rc;
     if ((rc = export_finish(ctx, neighbor_normals_out, ndev, (size_t)n * 12, out_mem))) return rc;
     if ((rc = export_finish(ctx, neighbor_index_out, idev, (size_t)n * 4, out_mem))) return rc;
+    ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ICP_OK;
+}
+
+int icp_knn_query(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int32_t k, float distance_upper_bound, int32_t flags,
+                  float* dist_out, int32_t* index_out, int out_mem) {
+    DeviceGuard device_guard(ctx);
+    if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    char why[160];
+    if (knn_query_refusals(n, k, flags, dist_out != nullptr, index_out != nullptr, mem, out_mem, why))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, why);
+    {   // iterations a chunked launch still holds back run against the map / configuration they were launched with
+        const int rc_held = continue_launch(ctx, -1);
+        if (rc_held) return rc_held;
+    }
+    if (ctx->in_registration || ctx->result_pending())
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_knn_query: registration in progress");
+    if (frame_in_flight(ctx)) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_knn_query: a frame is launched and awaits its end");
+    if (ctx->map_m <= 0 || !ctx->grid_valid) return fail(ctx, ICP_ERR_EMPTY_MAP, "the local map is empty");
+    if (n == 0) return ICP_OK;
+    // the grid is read, nothing else: the rows, the distances and the indices are staged in buffers of this entry point alone
+    const size_t cells = (size_t)n * (size_t)k;
+    const void* in;
+    int rc = import_buffer(ctx, xyz, (size_t)n * 12, mem, ctx->knn_in, &in);
+    if (rc) return rc;
+    void *ddev, *idev;
+    if ((rc = export_target(ctx, dist_out, cells * 4, out_mem, ctx->knn_dist, &ddev))) return rc;
+    if ((rc = export_target(ctx, index_out, cells * 4, out_mem, ctx->knn_idx, &idev))) return rc;
+    if ((rc = launch_knn_query(ctx, (const float*)in, n, k, knn_squared_bound(distance_upper_bound), flags & ICP_KNN_SQR_DISTS,
+                               (float*)ddev, (int32_t*)idev)))
+        return rc;
+    if ((rc = export_finish(ctx, dist_out, ddev, cells * 4, out_mem))) return rc;
+    if ((rc = export_finish(ctx, index_out, idev, cells * 4, out_mem))) return rc;
     ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ICP_OK;
 }

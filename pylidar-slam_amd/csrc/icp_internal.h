@@ -603,6 +603,7 @@ struct icp_ctx {
     int zbuf_clean_pixels = 0;
     icp::DeviceBuffer zbuf, stage_in, stage_out, stage_out2, flags, scan_a, scan_b, sort_tmp, keys_a, keys_b, vals_a,
         vals_b, counter;
+    icp::DeviceBuffer knn_in, knn_dist, knn_idx;  // staging of icp_knn_query alone: a query leaves every other buffer as it was
     // ---- projective local map (row a19)
     icp::DeviceBuffer pm_v, pm_n, pm_mv, pm_mn, pm_z, pm_tmp;
     std::vector<int> pm_slots;                 // storage slot of every kept map, oldest first
@@ -706,6 +707,13 @@ int launch_normals_install(icp_ctx* ctx, const float* by_index_dev);
 // indices_survive = false when the map is replaced wholesale)
 int stash_frame_seeds(icp_ctx* ctx, int64_t evicted, bool indices_survive);
 int run_seed_job(icp_ctx* ctx);
+GridView grid_view(icp_ctx* ctx);          // the kernels' view of the context's current grid
+int knn_fine_rings(const icp_ctx* ctx);    // fine rings a kNN search tries before it moves to the coarse level
+
+// ---- knn.hip
+// exact k nearest map points of n query rows (device pointers; either output may be null); b2: squared distance bound, +inf: none
+int launch_knn_query(icp_ctx* ctx, const float* xyz, int64_t n, int k, float b2, int sqr_dists, float* dist_out,
+                     int32_t* index_out);
 
 // ---- gauss_newton.hip
 AlignParams make_align_params(const icp_ctx* ctx);

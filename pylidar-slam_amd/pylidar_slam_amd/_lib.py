@@ -26,6 +26,8 @@ ICP_ERR_EMPTY_MAP = -4
 ICP_ERR_NO_DEVICE = -5
 ICP_ERR_EXCHANGE = -6
 BATCH_MAX_SEQUENCES = 32  # ICP_BATCH_MAX_SEQUENCES
+KNN_SQR_DISTS = 1  # ICP_KNN_SQR_DISTS
+KNN_MAX_K = 32
 
 STATUS_MESSAGES = {
     ICP_ERR_INVALID_ARGUMENT: "invalid argument",
@@ -135,6 +137,7 @@ EXPORTED_SYMBOLS = {
     "icp_handoff_fallbacks": (_INT, [_P]),
     "icp_map_get": (_INT, [_P, _P, _INT]),
     "icp_nearest_neighbor_search": (_INT, [_P, _P, _I64, _INT, _P, _P, _P, _INT]),
+    "icp_knn_query": (_INT, [_P, _P, _I64, _INT, C.c_int32, C.c_float, C.c_int32, _P, _P, _INT]),
     "icp_last_neighbors": (_INT, [_P, _P, _P, _INT]),
     "icp_compute_normal_map": (_INT, [_P, _P, _INT, _INT, _P, _INT]),
     "icp_compute_neighbors": (_INT, [_P, _P, _P, _P, _INT, _INT, _INT, _P, _P, _INT]),

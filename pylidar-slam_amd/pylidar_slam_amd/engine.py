@@ -484,6 +484,35 @@ class IcpContext:
                 ix.ctypes.data if ix is not None else None, MEM_HOST))
         return nb, nm, ix
 
+    def knn_query(self, points: Array, k: int = 1, distance_upper_bound: Optional[float] = None, sqr_dists: bool = False):
+        """`pykdtree.kdtree.KDTree(map).query(points, k)` (slam/odometry/local_map.py:369,385,405) against the map of this
+        context: the exact k nearest map points of every row of `points` [n, 3] (`icp_knn_query`; k = 1..32).  Returns
+        (dist [n, k] float32, index [n, k] int32): ascending by (distance, map index), indices in `map_points()` order;
+        `sqr_dists` returns the squared distances.  `distance_upper_bound` = b keeps neighbours with d2 < b * b only.  Entries
+        without a neighbour (fewer than k points within reach, a non-finite query row) are (+inf, `map_size()`).
+        numpy in -> numpy out, cuda tensor in -> cuda tensors out."""
+        self._bind(points)
+        p, mem, keep = _ptr_mem(points)
+        if keep.ndim != 2 or keep.shape[1] != 3:
+            raise AssertionError(f"knn_query: expected [n, 3] points, got {tuple(keep.shape)}")
+        n, k = int(keep.shape[0]), int(k)
+        bound = 0.0 if distance_upper_bound is None else float(distance_upper_bound)
+        if bound != bound or bound < 0.0:
+            raise AssertionError(f"knn_query: distance_upper_bound = {distance_upper_bound} is not a distance")
+        flags = _lib.KNN_SQR_DISTS if sqr_dists else 0
+        cols = max(k, 0)  # (k < 1 is the library's to refuse: it looks at k first)
+        # (one row at least: an empty array has no address, and the library tells an output from its absence by it)
+        if mem == MEM_DEVICE:
+            dist = torch.empty((max(n, 1), cols), dtype=torch.float32, device=keep.device)
+            index = torch.empty((max(n, 1), cols), dtype=torch.int32, device=keep.device)
+            dp, ip = dist.data_ptr(), index.data_ptr()
+        else:
+            dist, index = np.empty((max(n, 1), cols), np.float32), np.empty((max(n, 1), cols), np.int32)
+            dp, ip = dist.ctypes.data, index.ctypes.data
+        dist, index = dist[:n], index[:n]
+        self._check(self._lib.icp_knn_query(self._h, p if n else None, n, mem, k, bound, flags, dp, ip, mem))
+        return dist, index
+
     def last_neighbors(self, n: int):
         """(original map index per target, [3,4] pose) of the LAST iteration of the last registration, read back from the
         library's exact nearest-neighbour cache (test support: `icp_last_neighbors`)."""

@@ -99,3 +99,23 @@ def register_with_reference():
     except Exception:  # hydra absent: the enum patches are all the loaders need
         pass
     return odometry
+
+
+def install_kdtree():
+    """Places `pylidar_slam_amd.kdtree` at `sys.modules["pykdtree.kdtree"]` (under a parent package `pykdtree`), so that
+    `from pykdtree.kdtree import KDTree` — slam/odometry/local_map.py:12 — resolves to the MI355X search and the reference's
+    unmodified `KdTreeLocalMap` runs its queries (:385, :405) on the device.  A slam.* module that was imported before and
+    holds another `KDTree` is handed this one.  Returns the installed module."""
+    import types
+
+    from . import kdtree
+    parent = types.ModuleType("pykdtree")
+    parent.__path__ = []  # a package: `import pykdtree.kdtree` resolves through sys.modules
+    parent.kdtree = kdtree
+    sys.modules["pykdtree"] = parent
+    sys.modules["pykdtree.kdtree"] = kdtree
+    for name, mod in list(sys.modules.items()):
+        held = getattr(mod, "KDTree", None) if name.startswith("slam") else None
+        if held is not None and held is not kdtree.KDTree and getattr(held, "__module__", "").startswith("pykdtree"):
+            setattr(mod, "KDTree", kdtree.KDTree)
+    return kdtree
