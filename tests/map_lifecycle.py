@@ -457,10 +457,49 @@ def searched(name, i):
     return name != "drift" or i < 3 or i == len(script(name).ops) - 1
 
 
-def check_search(ctx, model, tag, seed, nref=None):
+BIT_ROWS = 512       # map points per search held to the bit model of the normals (tests/normals_audit.py)
+_BIT_MODELS = {}     # (bits of the map, k, seed) -> the model of the sampled rows: the entry points rebuild the same maps
+
+
+def check_normal_bits(tag, map_points, k, normals, seed, bits=True):
+    """BIT_ROWS map points (drawn by `seed`; all of a smaller map) of `normals` by index against the bit model of the kNN normals
+    — for normals the library ESTIMATED on this map (behind an insertion, or with "carry_normals" 0): carried normals are
+    rotated, not estimated, and have no bit model.  `bits` False (the oracle-backed contexts of the CPU suite, whose normals are
+    the reference's float32 SVD): the same points within the model's float64 bar of the truth and of the model instead.  Returns
+    the number of points compared."""
+    import hashlib
+    import normals_audit as NA
+    m = np.ascontiguousarray(map_points, F32)
+    normals = np.ascontiguousarray(normals, F32)
+    reached = np.flatnonzero(~np.isnan(normals).any(axis=1))
+    rows = reached if reached.size <= BIT_ROWS else np.sort(np.random.default_rng(seed + 2000).choice(reached, BIT_ROWS, False))
+    key = (hashlib.sha1(m.tobytes()).hexdigest(), int(k), rows.tobytes())
+    if key not in _BIT_MODELS:
+        _BIT_MODELS[key] = (NA.model_normals(m, int(k), rows=rows), None if bits else NA.truth_normals(m, int(k)))
+    want, truth = _BIT_MODELS[key]
+    NA.check_caps(want, tag)
+    if bits:
+        return NA.check_bits(normals, want, what=f"[normal bits] {tag}")
+    if truth is None:
+        truth = NA.truth_normals(m, int(k))
+        _BIT_MODELS[key] = (want, truth)
+    use = truth[2][rows] & ~want.left_out
+    if not use.any():
+        return 0
+    at = rows[use]
+    to_truth, _ = NA.truth_ratio(normals, truth, at)
+    to_model = float((NA.sin_angle(normals[at], want.normals[use]) * truth[1][at] / NA.U24).max())
+    assert to_truth <= NA.BAR and to_model <= NA.BAR, \
+        f"[normal bar] {tag}: {to_truth:.2f} (to float64) and {to_model:.2f} (to the model) of 2^-24 / gap, bar {NA.BAR:.2f}"
+    return int(use.sum())
+
+
+def check_search(ctx, model, tag, seed, nref=None, estimated=False, bits=True):
     """`nearest_neighbor_search(probes, with_index=True)` of search_probes(map, seed) against the model's map — `seed` is
     the index of the operation in its script, the rule test_census follows; an empty map raises as
-    test_tiny_maps_and_duplicates expects.  Returns (figures, NormalReference on the model's map, normals by index)."""
+    test_tiny_maps_and_duplicates expects.  `estimated`: the normals were estimated on this very map (not carried): they are
+    held to the bit model of tests/normals_audit.py as well (`bits` False, the oracle's normals: to its float64 bar, see
+    check_normal_bits).  Returns (figures, NormalReference on the model's map, normals by index)."""
     import pytest
     if not len(model):
         with pytest.raises(RuntimeError):
@@ -474,6 +513,7 @@ def check_search(ctx, model, tag, seed, nref=None):
     normals = np.full((len(m), 3), np.nan, F32)
     normals[ix] = nm
     fig["ix"] = ix
+    fig["normal_bits"] = check_normal_bits(tag, m, ctx.config.num_neighbors_normals, normals, seed, bits) if estimated else 0
     return fig, nref, normals
 
 

@@ -132,7 +132,7 @@ def _run(torch, name, entry, options=(), worst=None, normals_out=None, **kw):
     s = L.script(name)
     ctx, model = _ctx(s.local_map_size, options, **kw), L.MapModel(s.local_map_size)
     state = dict(scans=s.scans, frame=0)
-    figs = dict(share=0.0, mismatches=0, worst_tie=0.0, min_dot=1.0, ratio=0.0, searched=0, registered=0)
+    figs = dict(share=0.0, mismatches=0, worst_tie=0.0, min_dot=1.0, ratio=0.0, searched=0, registered=0, normal_bits=0)
     for i, op in enumerate(s.ops):
         tag = f"{name}/{entry} op {i} ({op.note or op.kind})"
         ins = _apply(torch, ctx, model, op, entry, i, state)
@@ -143,7 +143,14 @@ def _run(torch, name, entry, options=(), worst=None, normals_out=None, **kw):
             figs["registered"] += 1
             L.check_state(ctx, model, tag + " behind the registration")
         if L.searched(name, i):
-            fig, _, normals = L.check_search(ctx, model, tag, seed=i)
+            # behind a "set" or an inserting update the grid was rebuilt and every normal is estimated anew (so it is behind every
+            # operation with "carry_normals" 0): those are held to the bit model too; behind a pose-only update they are carried
+            # (the oracle-backed context of tests/test_map_lifecycle.py estimates every time, in the reference's arithmetic: the
+            # model's float64 bar instead of its bits)
+            from pylidar_slam_amd.engine import IcpContext
+            library = isinstance(ctx, IcpContext)
+            estimated = not library or op.cloud is not None or ("carry_normals", 0) in tuple(options)
+            fig, _, normals = L.check_search(ctx, model, tag, seed=i, estimated=estimated, bits=library)
             if normals_out is not None:
                 normals_out.append(normals)
             if fig is not None:
@@ -151,12 +158,13 @@ def _run(torch, name, entry, options=(), worst=None, normals_out=None, **kw):
                 for k in ("share", "mismatches", "worst_tie"):
                     figs[k] = max(figs[k], fig[k])
                 figs["min_dot"] = min(figs["min_dot"], fig["min_dot"])
+                figs["normal_bits"] += fig["normal_bits"]
     assert ctx.handoff_fallbacks() == 0
     ctx.close()
     print(f"{name}/{entry}{' ' + str(options) if options else ''}: {len(s.ops)} operations with the model's bits; "
           f"{figs['searched']} searches, mismatch share <= {figs['share']:.2e} ({figs['mismatches']} probes at most, worst tie "
           f"{figs['worst_tie']:.1e}), min |dot| {figs['min_dot']:.7f}; {figs['registered']} registrations audited; "
-          f"float64 ratio {figs['ratio']:.3f}")
+          f"float64 ratio {figs['ratio']:.3f}; {figs['normal_bits']} estimated normals bit-equal to their model")
     return figs
 
 
