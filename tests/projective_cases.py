@@ -379,6 +379,18 @@ def match_rows(rows, table):
     return np.where(hit, order[pos], -1)
 
 
+def bit_model_unequal(rows, points, h, w):
+    """`rows` [H*W,3] (the pixels of a vertex map as rows) against the bit model of the projection applied to `points` [n,3]
+    (NaN rows: no point): (the pixels whose three floats are not the bits of the model's winner — zeros where it has none —,
+    the number of pixels compared, the number of rows the model flags)."""
+    import projection_audit as PA
+    bit = PA.model(np.ascontiguousarray(points, F32), h, w, UP_FOV, DOWN_FOV)
+    skip = PA.excluded_pixels(bit)
+    got = np.ascontiguousarray(np.asarray(rows, F32).reshape(-1, 3))
+    differ = (got.view(np.uint32) != bit.rows.view(np.uint32)).any(axis=1) & ~skip
+    return np.flatnonzero(differ), int((~skip).sum()), int(bit.flagged.sum())
+
+
 def account_model(mv, mn, vmaps, nmaps, poses, h, w):
     """Every pixel of every layer of a model (`mv`, `mn` [K,3,H,W]) against the oracle's build_model of the same window
     (`vmaps`, `nmaps` [3,H,W] per layer and the bit-identical `poses`).  A pixel is
@@ -387,10 +399,15 @@ def account_model(mv, mn, vmaps, nmaps, poses, h, w):
       explained   another winner than the oracle's (or a winner on one side only), where (i) one of the two source points
                   has its reference row / column in the coin-toss band, or (ii) both land here with ranges within 2 float32
                   ulp of each other; the device's winner must still be bit-equal to the fma chain of a source pixel;
-      unexplained anything else."""
+      unexplained anything else.
+    Beside it the stricter accounting against the BIT MODEL of the projection (tests/projection_audit.py), which knows no coin
+    toss: `model_unequal` counts the pixels whose vertex is not, bit for bit, the winner of that model applied to the fma chain
+    of the layer's valid source pixels (pixel_of's validity, the lowest key) — zeros where the model has no winner;
+    `model_compared` the pixels compared (all but those a flagged row of the model can enter: `model_flagged` rows)."""
     mv, mn = np.asarray(mv, F32), np.asarray(mn, F32)
     npix = h * w
-    out = dict(occupied=0, equal=0, explained=0, worst_dv=0.0, worst_tol=0.0, unexplained=[], explained_pixels=set())
+    out = dict(occupied=0, equal=0, explained=0, worst_dv=0.0, worst_tol=0.0, unexplained=[], explained_pixels=set(),
+               model_unequal=0, model_compared=0, model_flagged=0, model_first=[])
     assert mv.shape == (len(vmaps), 3, h, w) and mn.shape == mv.shape, (mv.shape, len(vmaps))
     for k, (v, nm, pose) in enumerate(zip(vmaps, nmaps, poses)):
         src = O.vertex_map_to_points(np.asarray(v, F32))
@@ -412,6 +429,11 @@ def account_model(mv, mn, vmaps, nmaps, poses, h, w):
         didx = np.full(npix, -1, np.int64)
         didx[occ] = match_rows(lv[occ], table)
         out["occupied"] += int((occ | (oidx >= 0)).sum())
+        unequal, compared, flagged = bit_model_unequal(lv, table, h, w)
+        out["model_unequal"] += int(unequal.size)
+        out["model_compared"] += compared
+        out["model_flagged"] += flagged
+        out["model_first"] += [(k, int(p // w), int(p % w)) for p in unequal[:4]]
         # the common case in one sweep: the oracle's winner, the bits of its fma chain, within the transform tolerance
         safe = np.maximum(didx, 0)
         dv = np.abs(lv.astype(F64) - ora_pts[safe].astype(F64)).max(axis=1)
@@ -607,12 +629,26 @@ def account_association(rows, mv, mn, points, index_map, oracle_rows=None, model
     """`rows` = (neighbours, normals, targets) as returned.  Exact part: equal to expected_association, row by row.  Against
     the oracle's (`oracle_rows`, from `nearest_neighbor_search` of a LibraryWindowOracle): the sets of matched targets are
     equal apart from targets whose pixel — or one of its eight neighbours, columns wrapping — holds the reference pixel of
-    a target in the coin-toss band, or is an explained pixel of the model accounting."""
+    a target in the coin-toss band, or is an explained pixel of the model accounting.
+    Beside it, stricter: `model_unequal` counts the pixels of `index_map` whose winner is not the winner of the bit model of the
+    projection (tests/projection_audit.py) applied to `points`, and — the targets the search itself projected — the returned
+    target rows that are not, in pixel order, that model's winners at the pixels some layer of the model occupies."""
+    import projection_audit as PA
     nb, nn, tg = (np.asarray(a, F32).reshape(-1, 3) for a in rows)
     _, _, h, w = mv.shape
     pts = np.asarray(points, F32).reshape(-1, 3)
     enb, enn, etg, epix, eidx = expected_association(mv, mn, pts, index_map)
     out = dict(rows=int(tg.shape[0]), expected_rows=int(etg.shape[0]), explained=0, unexplained=[])
+    bit = PA.model(np.ascontiguousarray(pts), h, w, UP_FOV, DOWN_FOV)
+    skip = PA.excluded_pixels(bit)
+    out["model_unequal"] = int(((np.asarray(index_map).reshape(-1) != bit.index.reshape(-1)) & ~skip).sum())
+    out["model_flagged"] = int(bit.flagged.sum())
+    if not skip.any():
+        mtg = expected_association(mv, mn, pts, bit.index)[2]
+        if mtg.shape != tg.shape:
+            out["model_unequal"] += abs(int(mtg.shape[0]) - int(tg.shape[0])) or 1
+        else:
+            out["model_unequal"] += int((mtg.view(np.uint32) != np.ascontiguousarray(tg).view(np.uint32)).any(axis=1).sum())
     if tg.shape != etg.shape or not np.array_equal(tg, etg):
         out["unexplained"].append(("targets", "the matched targets / their order differ from the device's own pixels"))
         return out

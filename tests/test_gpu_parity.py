@@ -1186,6 +1186,7 @@ def test_projective_map_model_and_search(torch_cuda, O, golden_projective):
     model = PC.account_model(mv, mn, lib.vmaps, lib.nmaps, lib.poses, h, w)
     assert model["unexplained"] == [], model["unexplained"][:8]
     assert model["explained"] <= 0.005 * model["occupied"]
+    assert model["model_unequal"] == 0, model["model_first"]  # (the bit model: no coin toss)
     occ = np.abs(mv).max(axis=1) > 0
     assert (occ != (np.abs(orc.model_vmap).max(axis=1) > 0)).sum() <= 2 * model["explained"]
     same = occ & (np.abs(orc.model_vmap).max(axis=1) > 0)
@@ -1201,6 +1202,7 @@ def test_projective_map_model_and_search(torch_cuda, O, golden_projective):
                                  model["explained_pixels"])
     assert got["unexplained"] == [], got["unexplained"][:8]
     assert got["rows"] == got["expected_rows"] and got["explained"] <= max(3, got["rows"] // 2000)
+    assert got["model_unequal"] == 0, got
     onb, onm, otg = orc.nearest_neighbor_search(pts)
     assert abs(nb.shape[0] - onb.shape[0]) <= max(3, onb.shape[0] // 2000)
     print(f"projective model: explained {model['explained']} of {model['occupied']}; association: {got['rows']} rows, "

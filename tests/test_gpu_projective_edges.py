@@ -172,7 +172,7 @@ def test_window_and_model(torch_cuda, O, h, w, lms, ks, source):
     stock = O.ProjectiveLocalMapOracle(h, w, PC.UP_FOV, PC.DOWN_FOV, local_map_size=lms, normals_kernel_size=ks,
                                        normals_dtype=F64)
     ctx.pmap_init()
-    total = dict(occupied=0, equal=0, explained=0)
+    total = dict(occupied=0, equal=0, explained=0, model_unequal=0, model_compared=0, model_flagged=0)
     worst, drift_max, unexplained = (0.0, 0.0), 0.0, []
     calls = PC.window_sequence(h, w, lms, source)
     for n, (pose, v) in enumerate(calls):
@@ -197,6 +197,10 @@ def test_window_and_model(torch_cuda, O, h, w, lms, ks, source):
           f"{worst[0]:.2e} (bound {worst[1]:.2e}); pose drift from the stock oracle {drift_max:.2e}")
     assert unexplained == [], unexplained[:8]
     assert total["explained"] <= 0.005 * total["occupied"]
+    # beside it, stricter: every pixel of every layer is the winner of the bit model of the projection (no coin toss)
+    print(f"window {h}x{w} size {lms}: against the bit model, {total['model_compared']} pixels compared, "
+          f"{total['model_unequal']} unequal, {total['model_flagged']} rows flagged")
+    assert total["model_unequal"] == 0
     ctx.close()
 
 
@@ -231,6 +235,7 @@ def test_recorded_reference_model(torch_cuda, O):
           f"pixels: median {np.median(ang):.1e}, p99 {np.percentile(ang, 99):.1e}")
     assert dev["unexplained"] == [] and rec["unexplained"] == [], (dev["unexplained"][:4], rec["unexplained"][:4])
     assert dev["explained"] + rec["explained"] <= 0.005 * rec["occupied"]
+    assert dev["model_unequal"] == 0, dev["model_first"]
     assert both.sum() > 0.95 * rec["occupied"]
     assert np.median(ang) < 1e-3 and np.percentile(ang, 99) < 2e-2
     ctx.close()
@@ -255,7 +260,9 @@ def _associate(ctx, orc, pts, h, w):
     finite = np.where(np.isfinite(pts).all(axis=1)[:, None], pts, 0).astype(F32)
     model = PC.account_model(mv, mn, orc.vmaps, orc.nmaps, orc.poses, h, w)
     assert model["unexplained"] == []
+    assert model["model_unequal"] == 0, model["model_first"]
     got = PC.account_association(rows, mv, mn, pts, index, orc.nearest_neighbor_search(finite), model["explained_pixels"])
+    assert got["model_unequal"] == 0, got
     return rows, got, index
 
 
@@ -425,3 +432,78 @@ def test_edges_through_the_batch(torch_cuda):
 
 def O_points(vmap):
     return np.ascontiguousarray(vmap.reshape(3, -1).T)
+
+
+# ---- F. the projective kernels round with the projection's function: its boundary cloud through them ---------------------
+def _in_band(points, h, w):
+    import projection_audit as PA
+    row, col, r, _ = PA.coordinates(np.ascontiguousarray(points, F32), h, w, PC.UP_FOV, PC.DOWN_FOV, exact=False)
+    with np.errstate(invalid="ignore"):
+        return (PA.near_half(row) | PA.near_half(col)) & (r > 0)
+
+
+def test_boundary_cloud_as_the_window(torch_cuda, O):
+    """`k_pm_project` on the refinement branch: the boundary cloud of tests/projection_audit.py (a point on every row and column
+    boundary of the 16 x 128 image and its copies 1, 2, 3 ulp either side) planted as the vertex map of a window of size 1, at
+    the identity pose and — turned beforehand, so that the layer's pose puts it back on its boundaries — behind one pose-only
+    update by a yaw of 0.25 rad.  Every pixel of the layer is the winner of the bit model: no coin toss is granted."""
+    import projection_audit as PA
+    h, w = 16, 128
+    pl = PA.planted(h, w)
+    yaw = PA.yaw_pose()
+    for what, vmap, updates in (("identity", pl["vmap"], [(np.eye(4, dtype=F32), "vmap")]),
+                                ("yaw 0.25 rad", pl["vmap_turned"], [(np.eye(4, dtype=F32), "vmap"), (yaw, None)])):
+        ctx = _ctx(height=h, width=w, local_map_size=1)
+        orc = PC.LibraryWindowOracle(h, w, PC.UP_FOV, PC.DOWN_FOV, local_map_size=1,
+                                     nmap_of=lambda v: ctx.compute_normal_map(v, 5))
+        ctx.pmap_init()
+        for pose, v in updates:
+            v = np.array(vmap) if v is not None else None
+            ctx.pmap_update(pose, v)
+            orc.update(pose, v)
+        assert ctx.pmap_num_maps() == 1
+        mv, mn = ctx.pmap_model()
+        moved = PC.transform_fma(O.vertex_map_to_points(np.array(vmap)), orc.poses[0])
+        share = float(_in_band(moved, h, w).mean())
+        lv = O.vertex_map_to_points(mv[0])
+        unequal, compared, flagged = PC.bit_model_unequal(lv, moved, h, w)
+        print(f"boundary cloud as the window, {what}: {share:.0%} of {moved.shape[0]} source pixels in the refinement band, "
+              f"{compared} pixels compared with the bit model, {unequal.size} unequal, {flagged} rows flagged")
+        assert share > 0.9 and flagged == 0
+        assert unequal.size == 0, [(int(p // w), int(p % w)) for p in unequal[:8]]
+        got = PC.account_model(mv, mn, orc.vmaps, orc.nmaps, orc.poses, h, w)
+        assert got["model_unequal"] == 0 and got["unexplained"] == [], (got["model_first"], got["unexplained"][:4])
+        ctx.close()
+
+
+def test_boundary_cloud_as_the_targets(torch_cuda, O):
+    """`k_pm_project_targets` on the refinement branch: one forced iteration of `pmap_register` whose targets are the boundary
+    cloud (identity guess), and the cloud turned back by 0.25 rad (guess: that yaw), against a real map.  What the iteration
+    associated is visible in its step: the row count equals, and dx and the loss are within the bars of the E tests of, a host
+    Gauss-Newton step on the rows the BIT MODEL's pixels give; `pmap_nearest_neighbor_search` on the moved targets returns
+    exactly those rows."""
+    import projection_audit as PA
+    h, w = 16, 128
+    pl = PA.planted(h, w)
+    ctx = _ctx(height=h, width=w, local_map_size=1, max_num_alignments=1, threshold_delta_pose=0.0, sigma=PC.ROW_SIGMA)
+    ctx.pmap_init()
+    ctx.pmap_update(np.eye(4, dtype=F32), PC.scan_vmap(h, w))
+    mv, mn = ctx.pmap_model()
+    for what, targets, init in (("identity", np.array(pl["rows"]), np.eye(4, dtype=F32)),
+                                ("yaw 0.25 rad", np.array(pl["back"]), PA.yaw_pose())):
+        moved = PC.moved_targets(targets, init, False)
+        bit = PA.model(moved, h, w, PC.UP_FOV, PC.DOWN_FOV)
+        share = float(_in_band(moved, h, w).mean())
+        assert share > 0.9 and not bit.flagged.any(), (what, share)
+        want = PC.expected_association(mv, mn, moved, bit.index)[:3]
+        rows = ctx.pmap_nearest_neighbor_search(moved)
+        for a, b in zip(rows, want):
+            assert a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), b.view(np.uint32)), what
+        res = ctx.pmap_register(targets, init)
+        assert res.iterations == 1
+        ref = PC.host_step(want, "default", PC.ROW_SIGMA)
+        PC.assert_step(res.dx[0], float(res.losses[0]), res.num_targets, ref)
+        print(f"boundary cloud as the targets, {what}: {share:.0%} of {moved.shape[0]} targets in the refinement band, "
+              f"{res.num_targets} rows (the bit model: {ref[2]}), |dx| {float(np.abs(ref[0]).max()):.2e}, |dx - host| "
+              f"{float(np.abs(res.dx[0] - ref[0]).max()):.2e}")
+    ctx.close()
