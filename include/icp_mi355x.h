@@ -939,6 +939,73 @@ int icp_exchange_destroy(icp_ctx* ctx);
 int icp_map_normals_owned(icp_ctx* ctx, int32_t rank, int32_t world, float* normals_by_index);
 int icp_map_normals_install(icp_ctx* ctx, const float* normals_by_index);
 
+/* ---- aggregated world map: one point per voxel of everything a drive has seen, kept on the device -----------------------
+ * The first step of the reference's loop closure (slam/loop_closure.py:272-291: grid-sample every registered cloud, move it
+ * by its absolute pose — apply_pose / transform_pointcloud, slam/common/pose.py:40-49 —, concatenate a window of frames,
+ * re-express the window in the frame of its middle pose) as a persistent structure fed frame by frame.  A map belongs to
+ * the context it was created on: its work is enqueued on that context's stream, its errors are read with icp_last_error
+ * of that context, it is destroyed before the context is.  Several maps may live on one context; a map's buffers are its
+ * own, so an insert between icp_register_launch and icp_register_end is legal and leaves the registration untouched.
+ *   voxel size v > 0, capacity C >= 1 points, at most R >= 1 rows per insert, C + R <= 2^30.
+ *   world point  w = ((r0 x + r1 y) + r2 z) + t in float64, every product and sum rounded once; voxel c = rint(w / v),
+ *                half to even (the rounding of icp_grid_sample); the voxel key is the three coordinates themselves
+ *                (21 bits each): two voxels never merge.
+ *   set aside    a row with a non-finite w (counted in nonfinite), else with a coordinate outside [-2^20, 2^20)
+ *                (out_of_range): neither touches the map.
+ *   creation     a voxel is created by the first insert that reaches it; its point is the w of the row with the smallest
+ *                index among that insert's rows in the voxel, its first_frame that insert's frame_id.
+ *   updates      every finite in-range row that falls into a stored voxel — the creating insert's rows included — adds 1 to
+ *                the voxel's hits (uint32) and raises its last_frame to max(last_frame, frame_id).
+ *   order        stored points are numbered insert by insert, within an insert by ascending index of the creating rows.
+ *   capacity     of the voxels an insert would create the first ones in that order are stored while there is room; the
+ *                others stay unstored for good, and every row that falls into one of them — or, once the map holds C points,
+ *                into an unknown voxel — is counted in dropped.  No call fails because the map is full.
+ *   table        open addressing over the power of two at or above 2 (C + R) slots, first slot from the mixed key
+ *                (x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; slot = x & mask), linear probing; every probe ends
+ *                after as many steps as there are slots and sets bit 0 of the error word then.
+ *   footprint    24 bytes per slot + 32 per point of C + 16 per row of R (+ 12 per row of R in pinned host memory once
+ *                host rows have been inserted). */
+typedef struct icp_aggmap icp_aggmap;
+typedef struct {
+    int64_t size;         /* stored points */
+    int64_t inserts;      /* icp_aggmap_insert calls accepted since creation or the last clear */
+    int64_t dropped;      /* rows that fell into unstored or (full map) unknown voxels */
+    int64_t out_of_range; /* finite rows with a voxel coordinate outside [-2^20, 2^20) */
+    int64_t nonfinite;    /* rows whose world point is not finite */
+    int64_t error;        /* 0, or bit 0: a probe visited every slot (never seen: the table is at most half full) */
+} icp_aggmap_counters;
+/* a map for slam/loop_closure.py:272-291 (points moved by slam/common/pose.py:40-49); ICP_ERR_INVALID_ARGUMENT for v <= 0 or
+ * non-finite, C < 1, R < 1, C + R > 2^30 */
+int icp_aggmap_create(icp_ctx* ctx, double voxel_size, int64_t capacity, int64_t max_insert_rows, icp_aggmap** out);
+/* waits for the map's work, then frees it (slam/loop_closure.py:272-291, slam/common/pose.py:40-49: no counterpart) */
+void icp_aggmap_destroy(icp_aggmap* map);
+/* one registered cloud into the map: slam/loop_closure.py:272-291 per frame — the rows xyz [n,3] float32 moved by the
+ * absolute pose [4,4] float64, row-major, as transform_pointcloud does (slam/common/pose.py:40-49), in float64.  Three
+ * launches, asynchronous; host rows go through a pinned buffer of the map.  n = 0 counts as an insert and launches nothing.
+ * ICP_ERR_INVALID_ARGUMENT, before any launch, for n < 0, n > R, a non-finite pose entry, an unknown memory kind. */
+int icp_aggmap_insert(icp_aggmap* map, const float* xyz, int64_t n, int mem, const double pose[16], int32_t frame_id);
+/* the counters of the map behind everything enqueued (synchronises): how much of slam/loop_closure.py:272-291's
+ * concatenation — clouds moved by slam/common/pose.py:40-49 — the map holds and what it set aside */
+int icp_aggmap_stats(icp_aggmap* map, icp_aggmap_counters* out);
+/* the stored points in storage order, the concatenation of slam/loop_closure.py:272-291 (clouds moved by
+ * slam/common/pose.py:40-49): xyz_out [size,3] = float32(w - origin), subtracted in float64 and rounded once (origin NULL:
+ * zero); hits_out [size] uint32; first_frame_out / last_frame_out [size] int32.  Any output may be NULL; `cap` = rows the
+ * outputs have room for; *size_out = the map's size (also when ICP_ERR_INVALID_ARGUMENT says cap is below it).  Synchronises. */
+int icp_aggmap_get(icp_aggmap* map, const double origin[3], float* xyz_out, uint32_t* hits_out, int32_t* first_frame_out,
+                   int32_t* last_frame_out, int64_t cap, int out_mem, int64_t* size_out);
+/* ... the float64 world points w themselves [size,3] (slam/loop_closure.py:272-291, slam/common/pose.py:40-49) */
+int icp_aggmap_get_f64(icp_aggmap* map, double* xyz_out, int64_t cap, int out_mem, int64_t* size_out);
+/* the window of slam/loop_closure.py:272-291 (its lines :287-291): the stored points with frame_lo <= first_frame < frame_hi, in
+ * storage order, moved by `pose` [4,4] float64 — the inverse of the window's middle pose — with the float64 arithmetic of the
+ * insert (slam/common/pose.py:40-49) and rounded once to float32: xyz_out [count,3], index_out [count] int32 = their stored
+ * indices; `cap` = rows the outputs have room for; *count_out = rows of the window (also when ICP_ERR_INVALID_ARGUMENT says
+ * cap is below it).  ICP_ERR_INVALID_ARGUMENT for frame_lo > frame_hi, a non-finite pose entry, an unknown memory kind.
+ * Synchronises. */
+int icp_aggmap_submap(icp_aggmap* map, int32_t frame_lo, int32_t frame_hi, const double pose[16], float* xyz_out,
+                      int32_t* index_out, int64_t cap, int out_mem, int64_t* count_out);
+/* empties the map and keeps its memory (a new window of slam/loop_closure.py:272-291, slam/common/pose.py:40-49); asynchronous */
+int icp_aggmap_clear(icp_aggmap* map);
+
 /* ---- profiling hooks ---------------------------------------------------------------------------------------------
  * Accumulated HIP-event time (ms) and launch count of the dominant kernel (the per-iteration nearest-neighbour
  * search) since the last reset; measured on the context's stream.  `enable` is a bit mask: 1 = search kernel,

@@ -17,14 +17,9 @@
 #include <rocprim/rocprim.hpp>
 
 #include "icp_internal.h"
+#include "voxel_device.h"  // voxel_coord: int(np.round_(p / voxel)); rint = round-half-even
 
 namespace icp {
-
-template <typename T>
-__device__ inline long long voxel_coord(T v, double voxel) {
-    // int(np.round_(p / voxel)); rint = round-half-even
-    return (long long)rint((double)v / voxel);
-}
 
 template <typename T>
 __global__ void k_voxel_hash(const T* __restrict__ xyz, int n, double voxel, long long* __restrict__ voxels,

@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpPmapFrameConfig", "IcpFrameResult", "IcpBatchFrame", "load_library", "library_path",
+__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpPmapFrameConfig", "IcpFrameResult", "IcpBatchFrame", "IcpAggmapCounters", "load_library", "library_path",
            "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "FRAME_ROWS", "FRAME_VERTEX_MAP", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -91,6 +91,12 @@ class IcpBatchFrame(C.Structure):
     """icp_batch_frame: one member's frame of icp_batch_frame_launch."""
     _fields_ = [("xyz", C.c_void_p), ("n", C.c_int64), ("timestamps", C.c_void_p), ("init_pose", C.c_void_p),
                 ("skip", C.c_int32)]
+
+
+class IcpAggmapCounters(C.Structure):
+    """icp_aggmap_counters: what icp_aggmap_stats returns."""
+    _fields_ = [("size", C.c_int64), ("inserts", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64),
+                ("nonfinite", C.c_int64), ("error", C.c_int64)]
 
 
 _P = C.c_void_p
@@ -189,6 +195,14 @@ EXPORTED_SYMBOLS = {
     "icp_batch_odometry_init": (_INT, [_P, C.POINTER(IcpFrameConfig)]),
     "icp_batch_frame_launch": (_INT, [_P, C.POINTER(IcpBatchFrame), _INT]),
     "icp_batch_frame_end": (_INT, [_P, C.POINTER(IcpFrameResult), _P, _P, _P, _INT, _P, _P]),
+    "icp_aggmap_create": (_INT, [_P, C.c_double, _I64, _I64, C.POINTER(_P)]),
+    "icp_aggmap_destroy": (None, [_P]),
+    "icp_aggmap_insert": (_INT, [_P, _P, _I64, _INT, C.POINTER(C.c_double * 16), C.c_int32]),
+    "icp_aggmap_stats": (_INT, [_P, C.POINTER(IcpAggmapCounters)]),
+    "icp_aggmap_get": (_INT, [_P, C.POINTER(C.c_double * 3), _P, _P, _P, _P, _I64, _INT, C.POINTER(_I64)]),
+    "icp_aggmap_get_f64": (_INT, [_P, _P, _I64, _INT, C.POINTER(_I64)]),
+    "icp_aggmap_submap": (_INT, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_double * 16), _P, _P, _I64, _INT, C.POINTER(_I64)]),
+    "icp_aggmap_clear": (_INT, [_P]),
     "icp_normal_equations_ptr": (_P, [_P]),
     "icp_set_normal_equations_buffer": (_INT, [_P, _P]),
     "icp_profile_enable": (_INT, [_P, _INT]),

@@ -5,6 +5,7 @@ Accepts numpy arrays (host memory, staged by the library) and torch-ROCm tensors
 only — every computation happens in the HIP kernels behind the C ABI.
 """
 import ctypes as C
+import weakref
 from dataclasses import dataclass
 from typing import Optional, Tuple, Union
 
@@ -132,6 +133,8 @@ class IcpContext:
     # ------------------------------------------------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
+            for m in list(getattr(self, "_aggregated_maps", ())):  # (a map is destroyed before its context)
+                m.close()
             self._lib.icp_destroy(self._h)
             self._h = None
 
@@ -1006,6 +1009,12 @@ class IcpContext:
         return FrameResult(self._result(res.reg, losses, dxs), int(res.frame_index), bool(res.key_frame), int(res.samples),
                            int(res.inserted), points)
 
+    # ---- aggregated world map -----------------------------------------------------------------------------------------
+    def aggregated_map(self, voxel_size: float, capacity: int, max_insert_rows: int = 262144) -> "AggregatedMap":
+        """A voxel-de-duplicated world map on this context's device (`icp_aggmap_*`): one float64 point per voxel of edge
+        `voxel_size`, at most `capacity` points, fed by `insert` with at most `max_insert_rows` rows a call."""
+        return AggregatedMap(self, voxel_size, capacity, max_insert_rows)
+
     def raise_for_status(self, rc: int):
         """Maps a status code of the C ABI to the exception the reference raises (public form of the internal check)."""
         self._check(rc)
@@ -1033,6 +1042,142 @@ class IcpContext:
         v = C.c_double(0)
         self._check(self._lib.icp_profile_event_floor(self._h, int(samples), C.byref(v)))
         return float(v.value)
+
+
+def _pose16_f64(m) -> "C.Array":
+    a = np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(4, 4))
+    return (C.c_double * 16)(*a.reshape(-1).tolist())
+
+
+class AggregatedMap:
+    """The aggregated world map of a drive (`icp_aggmap_*`, include/icp_mi355x.h): the concatenation the reference's loop
+    closure builds from its registered clouds (slam/loop_closure.py:272-291), kept on the device with one point per voxel.
+
+    `insert(points, pose, frame_id)` moves the rows by the float64 absolute pose and is asynchronous; a voxel keeps the
+    float64 world point of the first row that reached it, in creation order, with its `hits`, `first_frame` and
+    `last_frame`.  Reads (`stats`, `points`, `hits`, ..., `submap`) synchronise.  Create it with
+    `IcpContext.aggregated_map`."""
+
+    def __init__(self, ctx: "IcpContext", voxel_size: float, capacity: int, max_insert_rows: int = 262144):
+        self._ctx, self._lib = ctx, ctx._lib
+        self.voxel_size, self.capacity, self.max_insert_rows = float(voxel_size), int(capacity), int(max_insert_rows)
+        self._h = None
+        h = C.c_void_p()
+        ctx._check(self._lib.icp_aggmap_create(ctx._h, self.voxel_size, self.capacity, self.max_insert_rows, C.byref(h)))
+        self._h = h
+        if not hasattr(ctx, "_aggregated_maps"):
+            ctx._aggregated_maps = weakref.WeakSet()
+        ctx._aggregated_maps.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
+            self._lib.icp_aggmap_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise AssertionError("the aggregated map has been closed")
+        return self._h
+
+    def insert(self, points: Array, pose, frame_id: int) -> None:
+        """The rows of `points` [n, 3] float32 (numpy: staged through pinned memory; cuda tensor: read in place) moved by
+        `pose` [4, 4] float64 into the map, as frame `frame_id`."""
+        h = self._handle()
+        self._ctx._bind(points)
+        p, mem, keep = _ptr_mem(points)
+        if keep.ndim != 2 or keep.shape[1] != 3:
+            raise AssertionError(f"AggregatedMap.insert: expected [n, 3] points, got {tuple(keep.shape)}")
+        n = int(keep.shape[0])
+        self._ctx._check(self._lib.icp_aggmap_insert(h, p if n else None, n, mem, C.byref(_pose16_f64(pose)), int(frame_id)))
+
+    def stats(self) -> dict:
+        """size, inserts, dropped, out_of_range, nonfinite and error of the map behind every insert so far (synchronises)."""
+        c = _lib.IcpAggmapCounters()
+        self._ctx._check(self._lib.icp_aggmap_stats(self._handle(), C.byref(c)))
+        return {k: int(getattr(c, k)) for k, _ in c._fields_}
+
+    def __len__(self) -> int:
+        return self.stats()["size"]
+
+    def _get(self, origin=None):
+        h, size = self._handle(), len(self)
+        xyz, hits = np.empty((size, 3), np.float32), np.empty(size, np.uint32)
+        first, last = np.empty(size, np.int32), np.empty(size, np.int32)
+        o = None if origin is None else C.byref((C.c_double * 3)(*np.asarray(origin, np.float64).reshape(3).tolist()))
+        got = C.c_int64(0)
+        self._ctx._check(self._lib.icp_aggmap_get(h, o, xyz.ctypes.data, hits.ctypes.data, first.ctypes.data, last.ctypes.data,
+                                                  size, MEM_HOST, C.byref(got)))
+        return xyz, hits, first, last
+
+    def points(self, origin=None, dtype=np.float32) -> np.ndarray:
+        """The stored points [size, 3] in creation order: float32(w - origin) (subtracted in float64, rounded once), or, with
+        dtype=float64, the world points w themselves (no origin then)."""
+        if np.dtype(dtype) == np.float64:
+            if origin is not None:
+                raise AssertionError("AggregatedMap.points: the float64 form returns the world points themselves (no origin)")
+            size = len(self)
+            xyz, got = np.empty((size, 3), np.float64), C.c_int64(0)
+            self._ctx._check(self._lib.icp_aggmap_get_f64(self._handle(), xyz.ctypes.data, size, MEM_HOST, C.byref(got)))
+            return xyz
+        if np.dtype(dtype) != np.float32:
+            raise AssertionError(f"AggregatedMap.points: float32 or float64, not {dtype}")
+        return self._get(origin)[0]
+
+    @property
+    def hits(self) -> np.ndarray:
+        """rows that fell into every stored voxel [size] uint32"""
+        return self._get()[1]
+
+    @property
+    def first_frame(self) -> np.ndarray:
+        """frame id of the insert that created every stored voxel [size] int32"""
+        return self._get()[2]
+
+    @property
+    def last_frame(self) -> np.ndarray:
+        """largest frame id among the rows of every stored voxel [size] int32"""
+        return self._get()[3]
+
+    def submap(self, lo: int, hi: int, pose):
+        """(points [m, 3] float32, stored indices [m] int32) of the voxels with lo <= first_frame < hi, in storage order,
+        moved by `pose` [4, 4] float64 — the window of slam/loop_closure.py:287-291 with the inverse of its middle pose."""
+        h, size = self._handle(), len(self)
+        xyz, index, got = np.empty((size, 3), np.float32), np.empty(size, np.int32), C.c_int64(0)
+        self._ctx._check(self._lib.icp_aggmap_submap(h, int(lo), int(hi), C.byref(_pose16_f64(pose)), xyz.ctypes.data,
+                                                     index.ctypes.data, size, MEM_HOST, C.byref(got)))
+        m = int(got.value)
+        return xyz[:m].copy(), index[:m].copy()
+
+    def clear(self) -> None:
+        """Empties the map; its memory stays."""
+        self._ctx._check(self._lib.icp_aggmap_clear(self._handle()))
+
+    def save_ply(self, path, origin=None, min_hits: int = 1) -> int:
+        """Binary little-endian PLY of the stored points with hits >= min_hits: x y z float (relative to `origin`), hits uint.
+        Returns the number of vertices written."""
+        xyz, hits, _, _ = self._get(origin)
+        return write_ply(path, xyz, hits, min_hits)
+
+
+def write_ply(path, xyz: np.ndarray, hits: np.ndarray, min_hits: int = 1) -> int:
+    """`AggregatedMap.save_ply` on arrays: plain Python and numpy."""
+    keep = np.asarray(hits) >= int(min_hits)
+    rows = np.empty(int(keep.sum()), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("hits", "<u4")])
+    kept = np.asarray(xyz, np.float32)[keep]
+    rows["x"], rows["y"], rows["z"], rows["hits"] = kept[:, 0], kept[:, 1], kept[:, 2], np.asarray(hits, np.uint32)[keep]
+    header = ("ply\nformat binary_little_endian 1.0\ncomment aggregated map, one point per voxel\n"
+              f"element vertex {len(rows)}\nproperty float x\nproperty float y\nproperty float z\nproperty uint hits\n"
+              "end_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rows.tobytes())
+    return len(rows)
 
 
 class IcpBatch:

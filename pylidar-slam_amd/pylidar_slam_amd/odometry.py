@@ -937,6 +937,14 @@ class MI355XICPConfig:
     # iterations, key frames, clouds, window and model, bit for bit.  numpy [N, 3], cuda [N, 3] and cuda [3, H, W] /
     # [1, 3, H, W] vertex-map frames; anything else is refused with the reason, and so is the flag on a kd-tree style map
     one_call_projective_frame: bool = False
+    # > 0: every frame's `odometry_pc` goes, with its float64 absolute pose and its frame index, into an aggregated world map on
+    # the device (`IcpContext.aggregated_map`, icp_aggmap_*: one float64 point per voxel of that edge, in creation order) —
+    # the concatenation the reference's loop closure starts from (slam/loop_closure.py:272-291), exposed as
+    # `odo.aggregated_map`.  Three launches behind every frame; the poses are the same, bit for bit.  0 (the default): no
+    # map is created and nothing is launched.  Frame 0 has no `odometry_pc` (the reference returns before it writes one,
+    # icp_odometry.py:176-181) and is not inserted
+    aggregate_map_voxel: float = 0.0
+    aggregate_map_capacity: int = 2000000  # points; rows in voxels beyond it are counted as dropped
 
 
 def _get(obj, key, default=None):
@@ -1018,6 +1026,14 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
             assert_debug(not bool(_get(config, "compact_sparse_vertex_map", False)),
                          "one_call_frame: compact_sparse_vertex_map is a schedule of the per-call path only")
             assert_debug(hasattr(self.ctx, "frame_launch"), "one_call_frame needs the library's frame calls")
+        self.aggregated_map = None
+        voxel = float(_get(config, "aggregate_map_voxel", 0.0) or 0.0)
+        assert_debug(voxel >= 0.0, f"aggregate_map_voxel = {voxel} is negative")
+        if voxel > 0.0:
+            assert_debug(hasattr(self.ctx, "aggregated_map"), "aggregate_map_voxel needs the library's aggregated map")
+            self.aggregated_map = self.ctx.aggregated_map(
+                voxel, int(_get(config, "aggregate_map_capacity", 2000000)),
+                max_insert_rows=max(262144, int(projector.height) * int(projector.width)))
         self._one_call_pmap = bool(_get(config, "one_call_projective_frame", False))
         if self._one_call_pmap:
             assert_debug(self._projective, "one_call_projective_frame: the projective frame calls of the library run the "
@@ -1035,6 +1051,20 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         self.local_map.init()
         self._iter = 0
         self._delta_since_map_update = np.eye(4, dtype=np.float32)
+        if self.aggregated_map is not None:
+            self.aggregated_map.clear()
+
+    def _aggregate(self, data_dict: dict, device_rows=None):
+        """`aggregate_map_voxel` > 0: the frame's `odometry_pc` into the aggregated map, with the absolute pose just appended
+        and the frame index.  `device_rows`: the frame's [N, 3] point rows where they are still on the device — inserted from
+        there (the same rows as `odometry_pc`; a row with a NaN, which `odometry_pc` leaves out, is set aside by the map and
+        counted as non-finite); otherwise the host rows of `odometry_pc` are inserted."""
+        if self.aggregated_map is None:
+            return
+        rows = device_rows if device_rows is not None else data_dict[self.pointcloud_key()]
+        if isinstance(rows, torch.Tensor) and not rows.is_cuda:
+            rows = rows.numpy()
+        self.aggregated_map.insert(rows, self.absolute_poses[-1], self._iter)
 
     def _warn_handoff_fallbacks(self):
         """Once per sequence (VERDICT r5 Weak #14): registrations whose pose hand-off inside a launch timed out were finished
@@ -1194,6 +1224,7 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
                                                                                  np.float64)))  # :200-202
         data_dict[self.pointcloud_key()] = tgt_np_pc  # :243
         data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+        self._aggregate(data_dict, self._tgt_pc if (want_rows and self._tgt_pc.is_cuda and not self._pc_is_pixels) else None)
         self._iter += 1
 
     def _one_call_next_frame(self, data_dict: dict):
@@ -1253,6 +1284,7 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
             tgt_np_pc = res.points.copy()
         data_dict[self.pointcloud_key()] = tgt_np_pc if want_rows else data_dict["distorted"]  # :243
         data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+        self._aggregate(data_dict, data if (want_rows and not is_numpy and data.ndim == 2) else None)
         self._iter += 1
 
     def _one_call_pmap_next_frame(self, data_dict: dict):
@@ -1321,6 +1353,7 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
             tgt_np_pc = res.points  # (a view of the fresh array the call filled: nobody else holds it)
         data_dict[self.pointcloud_key()] = tgt_np_pc if want_rows else data_dict["distorted"]  # :243
         data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+        self._aggregate(data_dict, data if (want_rows and not is_numpy and data.ndim == 2) else None)
         self._iter += 1
 
     # ---- host <-> device traffic of a frame, kept off the critical path ----------------------------------------------
@@ -1577,6 +1610,7 @@ class MI355XICPFrameToModelBatch:
                 pcs[b] = res.points.copy()
             d[m.pointcloud_key()] = pcs[b] if want[b] else d["distorted"]  # :243
             d[m.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+            m._aggregate(d, frames[b] if (want[b] and not is_numpy and frames[b].ndim == 2) else None)
             m._iter += 1
         self._iter += 1
         if error is not None:
@@ -1655,6 +1689,7 @@ class MI355XICPFrameToModelBatch:
                 pcs[b] = res.points  # (a view of the fresh array the call filled: nobody else holds it)
             d[m.pointcloud_key()] = pcs[b] if want[b] else d["distorted"]  # :243
             d[m.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
+            m._aggregate(d, frames[b] if (want[b] and not is_numpy and frames[b].ndim == 2) else None)
             m._iter += 1
         self._iter += 1
         if error is not None:
@@ -1721,6 +1756,7 @@ class MI355XICPFrameToModelBatch:
             m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
             d[m.pointcloud_key()] = pc  # :243
             d[m.relative_pose_key()] = res.pose.reshape(4, 4).copy()  # :244
+            m._aggregate(d, m._tgt_pc if ("distorted" not in d and m._tgt_pc.is_cuda and not m._pc_is_pixels) else None)
             m._iter += 1
         self._iter += 1
 
@@ -1765,5 +1801,6 @@ class MI355XICPFrameToModelBatch:
             m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
             d[m.pointcloud_key()] = pc  # :243
             d[m.relative_pose_key()] = res.pose.reshape(4, 4).copy()  # :244
+            m._aggregate(d, m._tgt_pc if ("distorted" not in d and m._tgt_pc.is_cuda and not m._pc_is_pixels) else None)
             m._iter += 1
         self._iter += 1
