@@ -1006,6 +1006,69 @@ int icp_aggmap_submap(icp_aggmap* map, int32_t frame_lo, int32_t frame_hi, const
 /* empties the map and keeps its memory (a new window of slam/loop_closure.py:272-291, slam/common/pose.py:40-49); asynchronous */
 int icp_aggmap_clear(icp_aggmap* map);
 
+/* ---- elevation image: a cloud rasterised top-down, the highest point per pixel ------------------------------------------
+ * ElevationImageRegistration.build_image of the reference (slam/common/registration.py:196-241), which its loop closure calls
+ * on every aggregated window (slam/loop_closure.py:294) and its elevation-image initialisation on every raw scan
+ * (slam/initialization.py:176).  An image belongs to the context it was created on, like an aggregated map: its work goes on
+ * that context's stream, its buffers are its own (a build between icp_register_launch and icp_register_end is legal and leaves
+ * the registration untouched), it is destroyed before the context is.  Several images may live on one context.
+ *   pixel      row = rint(x / pixel_size + H / 2), column = rint(y / pixel_size + W / 2), half to even, in the type of the
+ *              rows: for float32 rows pixel_size is rounded to float32 and division and sum are float32 operations, for
+ *              float64 rows everything is float64.  H / 2, W / 2: floor divisions.  A row is in the image iff
+ *              0 <= row < H and 0 <= column < W; a NaN or infinite x or y is outside.
+ *   height     z clipped to [z_min, z_max], the bounds rounded to the rows' type (+-inf clip like any value), -0.0 made +0.0.
+ *              The pixel goes to the greatest clipped z, with `flip` to the smallest.  Among rows of EQUAL clipped z the
+ *              highest row index wins, flipped or not (the reference leaves ties to an unstable sort: it has no rule).
+ *   theta      (clipped z - z_min) / (z_max - z_min): the denominator subtracted in float64 and rounded to the rows' type,
+ *              subtraction and division in the rows' type, stored as float32.  An empty pixel holds float32(z_min), not 0.
+ *   colour     `lut` [259,3] uint8 = 256 colours, then the under, over and bad colour (for a matplotlib colour map
+ *              uint8(lut[:, :3] * 255.0)); its row is matplotlib's for a float32 image: t = theta * 256 in float32, t == 256
+ *              becomes 255; NaN: 258, t < 0: 256, t >= 256: 257, else trunc(t).
+ *   outputs    rgb [H,W,3] uint8; theta [H,W] float32; points [H,W,3] float32: the winning row rounded once to float32, zeros
+ *              where the pixel is empty (`points_3D`); index [H,W] int32: the winning row, -1 where empty (`pc_indices`).
+ *   deviation  a row in the image whose z is NaN is set aside and counted in rows_nan_z; in the reference it wins its pixel
+ *              (argsort puts NaN last, the order is then reversed) and paints it with the bad colour.
+ *   launches   clear, splat, resolve on the context's stream, no host read: float32 rows are splat in one pass (64-bit
+ *              atomic maximum of the ordered bits of the clipped z above the row), float64 rows and map windows in two (the
+ *              extreme z of the pixel, then the highest row among the rows that have it).
+ *   footprint  35 bytes per pixel + 9 KB + 24 per row of max_rows (and as much pinned host memory) once host rows have been built
+ *              from. */
+typedef struct icp_elevation icp_elevation;
+typedef enum { ICP_ELEVATION_F32 = 0, ICP_ELEVATION_F64 = 1 } icp_elevation_dtype;
+typedef struct {
+    int64_t rows_in_image; /* rows of the last build inside the image with a z that is no NaN */
+    int64_t rows_outside;  /* rows outside the image (a NaN or infinite x or y among them) */
+    int64_t rows_nan_z;    /* rows inside the image set aside for a NaN z */
+    int64_t filled_pixels; /* pixels that hold a row */
+} icp_elevation_counters;
+/* an image object for slam/common/registration.py:196-241 with the settings of its constructor (:185-194): H x W pixels of
+ * pixel_size, the clip range, flip_z_axis, the colour table [259,3] uint8 in host memory (copied), at most max_rows rows a
+ * build.  ICP_ERR_INVALID_ARGUMENT for a pixel_size that is not positive and finite, a non-finite bound, z_min >= z_max (also
+ * once rounded to float32), H < 1, W < 1, H x W > 2^31 - 1, max_rows < 1 or > 2^31 - 1, a NULL table. */
+int icp_elevation_create(icp_ctx* ctx, int64_t height, int64_t width, double pixel_size, double z_min, double z_max, int flip,
+                         const uint8_t* lut, int64_t max_rows, icp_elevation** out);
+/* waits for the image's work, then frees it (slam/common/registration.py:196-241: no counterpart) */
+void icp_elevation_destroy(icp_elevation* img);
+/* slam/common/registration.py:196-241 on the rows xyz [n,3] of `dtype` (icp_elevation_dtype), as slam/initialization.py:176
+ * calls it on a raw scan: asynchronous, three launches (float64 rows: four); host rows go through a pinned buffer of the
+ * image, device rows are read in place and must stay untouched until the stream has passed the build.  n = 0 builds the
+ * empty image.  ICP_ERR_INVALID_ARGUMENT, before any launch, for n < 0, n > max_rows, n > 2^31 - 1, an unknown memory kind
+ * or dtype. */
+int icp_elevation_build(icp_elevation* img, const void* xyz, int64_t n, int mem, int dtype);
+/* slam/common/registration.py:196-241 as slam/loop_closure.py:294 calls it, on the window of slam/loop_closure.py:287-291
+ * without materialising it: the stored points of `map` with frame_lo <= first_frame < frame_hi, each moved by `pose` [4,4]
+ * float64 with the arithmetic of icp_aggmap_submap, splat as float64 rows.  index = the stored index; points = the moved point
+ * rounded once to float32 — for every filled pixel the row icp_aggmap_submap returns for that stored index, bit for bit.
+ * Asynchronous, four launches, the map's size is read on the device.  ICP_ERR_INVALID_ARGUMENT, before any launch, for a map
+ * of another context, frame_lo > frame_hi, a non-finite pose entry. */
+int icp_elevation_build_aggmap(icp_elevation* img, icp_aggmap* map, int32_t frame_lo, int32_t frame_hi, const double pose[16]);
+/* what slam/common/registration.py:196-241 returns, of the last build: rgb_out [H,W,3] uint8 (:229-230), theta_out [H,W] float32
+ * (:227-228), points_out [H,W,3] float32 (:233-236), index_out [H,W] int32 (:238-239).  Any output may be NULL.  Copies to host
+ * or device memory behind the build; synchronises only for host outputs.  ICP_ERR_INVALID_ARGUMENT for an unknown memory kind. */
+int icp_elevation_get(icp_elevation* img, uint8_t* rgb_out, float* theta_out, float* points_out, int32_t* index_out, int out_mem);
+/* the counters of the last build (synchronises): what slam/common/registration.py:196-241 kept (:205), dropped and painted */
+int icp_elevation_stats(icp_elevation* img, icp_elevation_counters* out);
+
 /* ---- profiling hooks ---------------------------------------------------------------------------------------------
  * Accumulated HIP-event time (ms) and launch count of the dominant kernel (the per-iteration nearest-neighbour
  * search) since the last reset; measured on the context's stream.  `enable` is a bit mask: 1 = search kernel,

@@ -33,38 +33,11 @@
 #include <new>
 
 #include "aggmap_plan.h"
+#include "aggmap_device.h"
 #include "icp_internal.h"
 #include "voxel_device.h"
 
 namespace icp {
-
-static constexpr int AGG_NEW = -1;       // the slot's voxel is not numbered yet (free slot, or claimed by the insert in progress)
-static constexpr int AGG_UNSTORED = -2;  // claimed beyond the capacity: never stored
-
-struct AggSlot {
-    int cand;       // smallest row of the creating insert in this voxel (INT_MAX: none yet)
-    int idx;        // stored index, AGG_NEW or AGG_UNSTORED
-    unsigned hits;  // rows that fell into the voxel
-    int last;       // largest frame id among them
-};
-
-struct AggPose {
-    double m[12];  // rows 0-2 of the 4x4 pose
-};
-
-struct AggCounters {
-    int size[2];  // stored points: the cell of the current parity is valid, the emit launch writes the other one
-    int error;
-    int sub_count;  // rows of the last submap
-    unsigned long long dropped, out_of_range, nonfinite;
-    unsigned long long pad[4];
-};
-static_assert(sizeof(AggCounters) == 72, "AggCounters layout");
-
-__device__ __forceinline__ double agg_world(const AggPose& p, int r, double x, double y, double z) {
-    return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(p.m[4 * r], x), __dmul_rn(p.m[4 * r + 1], y)), __dmul_rn(p.m[4 * r + 2], z)),
-                     p.m[4 * r + 3]);
-}
 
 __device__ __forceinline__ unsigned long long agg_wave_sum(unsigned long long v) {
 #pragma unroll
@@ -336,28 +309,6 @@ __global__ __launch_bounds__(AGGMAP_THREADS) void k_aggmap_sub_emit(const double
 }  // namespace icp
 
 using namespace icp;
-
-struct icp_aggmap {
-    icp_ctx* ctx = nullptr;
-    double voxel = 0.0;
-    int64_t capacity = 0, max_rows = 0;
-    uint64_t slots = 0;
-    int64_t inserts = 0;
-    int parity = 0;                      // the size cell the next launch reads
-    unsigned long long* keys = nullptr;  // [slots]
-    AggSlot* meta = nullptr;             // [slots]
-    double* pts = nullptr;               // [capacity][3]
-    int* first_frame = nullptr;          // [capacity]
-    int* slot_of = nullptr;              // [capacity]
-    int* row_slot = nullptr;             // [max_rows]
-    int* counts = nullptr;               // [AGGMAP_MAX_BLOCKS + 1]
-    AggCounters* cnt = nullptr;
-    float* stage_dev = nullptr;          // [max_rows][3]: host rows on their way in (allocated by the first host insert)
-    float* stage_host = nullptr;         // ... pinned
-    hipEvent_t stage_copied = nullptr;   // the last host insert's copy has left the pinned buffer
-    AggCounters* cnt_host = nullptr;     // pinned
-    DeviceBuffer out_xyz, out_a, out_b, out_c;  // outputs bound for host memory
-};
 
 namespace {
 

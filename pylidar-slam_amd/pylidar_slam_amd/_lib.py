@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpPmapFrameConfig", "IcpFrameResult", "IcpBatchFrame", "IcpAggmapCounters", "load_library", "library_path",
+__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpPmapFrameConfig", "IcpFrameResult", "IcpBatchFrame", "IcpAggmapCounters", "IcpElevationCounters", "load_library", "library_path",
            "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "FRAME_ROWS", "FRAME_VERTEX_MAP", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -98,6 +98,15 @@ class IcpAggmapCounters(C.Structure):
     _fields_ = [("size", C.c_int64), ("inserts", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64),
                 ("nonfinite", C.c_int64), ("error", C.c_int64)]
 
+
+class IcpElevationCounters(C.Structure):
+    """icp_elevation_counters: what icp_elevation_stats returns."""
+    _fields_ = [("rows_in_image", C.c_int64), ("rows_outside", C.c_int64), ("rows_nan_z", C.c_int64),
+                ("filled_pixels", C.c_int64)]
+
+
+ELEVATION_F32, ELEVATION_F64 = 0, 1  # icp_elevation_dtype
+ELEVATION_LUT_ROWS = 259
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -203,6 +212,12 @@ EXPORTED_SYMBOLS = {
     "icp_aggmap_get_f64": (_INT, [_P, _P, _I64, _INT, C.POINTER(_I64)]),
     "icp_aggmap_submap": (_INT, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_double * 16), _P, _P, _I64, _INT, C.POINTER(_I64)]),
     "icp_aggmap_clear": (_INT, [_P]),
+    "icp_elevation_create": (_INT, [_P, _I64, _I64, C.c_double, C.c_double, C.c_double, _INT, _P, _I64, C.POINTER(_P)]),
+    "icp_elevation_destroy": (None, [_P]),
+    "icp_elevation_build": (_INT, [_P, _P, _I64, _INT, _INT]),
+    "icp_elevation_build_aggmap": (_INT, [_P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_double * 16)]),
+    "icp_elevation_get": (_INT, [_P, _P, _P, _P, _P, _INT]),
+    "icp_elevation_stats": (_INT, [_P, C.POINTER(IcpElevationCounters)]),
     "icp_normal_equations_ptr": (_P, [_P]),
     "icp_set_normal_equations_buffer": (_INT, [_P, _P]),
     "icp_profile_enable": (_INT, [_P, _INT]),

@@ -133,8 +133,8 @@ class IcpContext:
     # ------------------------------------------------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
-            for m in list(getattr(self, "_aggregated_maps", ())):  # (a map is destroyed before its context)
-                m.close()
+            for m in list(getattr(self, "_elevation_images", ())) + list(getattr(self, "_aggregated_maps", ())):
+                m.close()  # (an image or a map is destroyed before its context)
             self._lib.icp_destroy(self._h)
             self._h = None
 
@@ -1015,6 +1015,12 @@ class IcpContext:
         `voxel_size`, at most `capacity` points, fed by `insert` with at most `max_insert_rows` rows a call."""
         return AggregatedMap(self, voxel_size, capacity, max_insert_rows)
 
+    def elevation_image(self, height: int = 400, width: int = 400, pixel_size: float = 0.4, z_min: float = 0.0,
+                        z_max: float = 5.0, flip_z_axis: bool = False, color_map="jet", max_rows: int = 262144) -> "ElevationImage":
+        """A top-down elevation image on this context's device (`icp_elevation_*`): `ElevationImageRegistration.build_image`
+        of the reference with the settings of its constructor.  `color_map`: a matplotlib name, or a [259, 3] uint8 table."""
+        return ElevationImage(self, height, width, pixel_size, z_min, z_max, flip_z_axis, color_map, max_rows)
+
     def raise_for_status(self, rc: int):
         """Maps a status code of the C ABI to the exception the reference raises (public form of the internal check)."""
         self._check(rc)
@@ -1154,6 +1160,12 @@ class AggregatedMap:
         m = int(got.value)
         return xyz[:m].copy(), index[:m].copy()
 
+    def elevation(self, lo: int, hi: int, pose, image: "ElevationImage") -> "ElevationImage":
+        """The elevation image of the window lo <= first_frame < hi moved by `pose`, built into `image` on the device without
+        materialising the window (`ElevationImage.build_from`); returns `image`."""
+        image.build_from(self, lo, hi, pose)
+        return image
+
     def clear(self) -> None:
         """Empties the map; its memory stays."""
         self._ctx._check(self._lib.icp_aggmap_clear(self._handle()))
@@ -1178,6 +1190,148 @@ def write_ply(path, xyz: np.ndarray, hits: np.ndarray, min_hits: int = 1) -> int
         f.write(header.encode("ascii"))
         f.write(rows.tobytes())
     return len(rows)
+
+
+def colormap_table(color_map="jet") -> np.ndarray:
+    """The [259, 3] uint8 table of a 256-colour matplotlib colour map (a name or a Colormap): its 256 colours, then its under,
+    over and bad colour, each `uint8(rgba[:3] * 255.0)` — the conversion slam/common/registration.py:229-230 applies to every
+    pixel.  matplotlib is imported here and nowhere else."""
+    import matplotlib
+    cmap = matplotlib.colormaps[color_map] if isinstance(color_map, str) else color_map
+    if int(cmap.N) != 256:
+        raise AssertionError(f"colormap_table: a colour map of 256 colours is needed, {cmap.name} has {cmap.N}")
+    rgba = np.concatenate([np.asarray(cmap(np.arange(256)), np.float64).reshape(256, 4),
+                           np.asarray([cmap.get_under(), cmap.get_over(), cmap.get_bad()], np.float64).reshape(3, 4)])
+    return (rgba[:, :3] * 255.0).astype(np.uint8)
+
+
+class ElevationImage:
+    """`ElevationImageRegistration.build_image` of the reference (slam/common/registration.py:196-241) on the device
+    (`icp_elevation_*`, include/icp_mi355x.h): the highest point per pixel of a top-down H x W image, as colour (`rgb`), `theta`,
+    the float32 point behind every pixel (`points_3d`) and its row (`indices`, -1 where the pixel is empty).
+
+    `build(points)` takes float32 or float64 rows (numpy: staged through pinned memory; cuda tensor: read in place);
+    `build_from(map, lo, hi, pose)` rasterises a frame window of an `AggregatedMap`.  Both are asynchronous; the properties
+    copy to the host and synchronise, `device(...)` returns cuda tensors without a host read.  Among rows of equal clipped z the
+    highest row wins; a row whose z is NaN is set aside (`stats()["rows_nan_z"]`).  Create it with `IcpContext.elevation_image`."""
+
+    def __init__(self, ctx: "IcpContext", height: int = 400, width: int = 400, pixel_size: float = 0.4, z_min: float = 0.0,
+                 z_max: float = 5.0, flip_z_axis: bool = False, color_map="jet", max_rows: int = 262144):
+        self._ctx, self._lib, self._h, self._keep = ctx, ctx._lib, None, None
+        self.height, self.width, self.pixel_size = int(height), int(width), float(pixel_size)
+        self.z_min, self.z_max, self.flip_z_axis, self.max_rows = float(z_min), float(z_max), bool(flip_z_axis), int(max_rows)
+        table = color_map if isinstance(color_map, np.ndarray) else colormap_table(color_map)
+        if table.dtype != np.uint8 or table.shape != (_lib.ELEVATION_LUT_ROWS, 3):
+            raise AssertionError(f"ElevationImage: the colour table is [259, 3] uint8, not {table.dtype} {tuple(table.shape)}")
+        self.table = np.ascontiguousarray(table)
+        h = C.c_void_p()
+        ctx._check(self._lib.icp_elevation_create(ctx._h, self.height, self.width, self.pixel_size, self.z_min, self.z_max,
+                                                  int(self.flip_z_axis), self.table.ctypes.data, self.max_rows, C.byref(h)))
+        self._h = h
+        if not hasattr(ctx, "_elevation_images"):
+            ctx._elevation_images = weakref.WeakSet()
+        ctx._elevation_images.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
+            self._lib.icp_elevation_destroy(self._h)
+        self._h = self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise AssertionError("the elevation image has been closed")
+        return self._h
+
+    def build(self, points: Array) -> None:
+        """The image of the rows `points` [n, 3], float32 or float64 (any other type is converted to float32)."""
+        h = self._handle()
+        self._ctx._bind(points)
+        if isinstance(points, torch.Tensor) and points.is_cuda:
+            t = points if points.dtype in (torch.float32, torch.float64) else points.to(torch.float32)
+            keep, mem, f64 = t.contiguous(), MEM_DEVICE, t.dtype == torch.float64
+            ptr = keep.data_ptr()
+        else:
+            a = points.numpy() if isinstance(points, torch.Tensor) else np.asarray(points)
+            keep = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+            mem, f64, ptr = MEM_HOST, keep.dtype == np.float64, keep.ctypes.data
+        if keep.ndim != 2 or keep.shape[1] != 3:
+            raise AssertionError(f"ElevationImage.build: expected [n, 3] points, got {tuple(keep.shape)}")
+        n = int(keep.shape[0])
+        self._ctx._check(self._lib.icp_elevation_build(h, ptr if n else None, n, mem,
+                                                       _lib.ELEVATION_F64 if f64 else _lib.ELEVATION_F32))
+        self._keep = keep if mem == MEM_DEVICE else None  # (device rows are read in place, behind this call)
+
+    def build_from(self, aggregated_map: "AggregatedMap", lo: int, hi: int, pose) -> None:
+        """The image of the stored points of `aggregated_map` with lo <= first_frame < hi, moved by `pose` [4, 4] float64 as
+        `AggregatedMap.submap` moves them; `indices` are stored indices."""
+        self._ctx._check(self._lib.icp_elevation_build_aggmap(self._handle(), aggregated_map._handle(), int(lo), int(hi),
+                                                              C.byref(_pose16_f64(pose))))
+        self._keep = None
+
+    def stats(self) -> dict:
+        """rows_in_image, rows_outside, rows_nan_z and filled_pixels of the last build (synchronises)."""
+        c = _lib.IcpElevationCounters()
+        self._ctx._check(self._lib.icp_elevation_stats(self._handle(), C.byref(c)))
+        return {k: int(getattr(c, k)) for k, _ in c._fields_}
+
+    _OUTPUTS = {"rgb": (0, np.uint8, torch.uint8, 3), "theta": (1, np.float32, torch.float32, 0),
+                "points_3d": (2, np.float32, torch.float32, 3), "indices": (3, np.int32, torch.int32, 0)}
+
+    def _shape(self, last):
+        return (self.height, self.width, last) if last else (self.height, self.width)
+
+    def _host(self, name) -> np.ndarray:
+        slot, dtype, _, last = self._OUTPUTS[name]
+        out = np.empty(self._shape(last), dtype)
+        args = [None] * 4
+        args[slot] = out.ctypes.data
+        self._ctx._check(self._lib.icp_elevation_get(self._handle(), *args, MEM_HOST))
+        return out
+
+    def device(self, *names) -> Tuple[torch.Tensor, ...]:
+        """cuda tensors of the named outputs ("rgb", "theta", "points_3d", "indices"; none named: all four), copied on the
+        device behind the build, on torch's current stream: no host read."""
+        names = names or tuple(self._OUTPUTS)
+        self._ctx.use_torch_stream()
+        args, outs = [None] * 4, []
+        for name in names:
+            slot, _, dtype, last = self._OUTPUTS[name]
+            outs.append(torch.empty(self._shape(last), dtype=dtype, device=self._ctx.device))
+            args[slot] = outs[-1].data_ptr()
+        self._ctx._check(self._lib.icp_elevation_get(self._handle(), *args, MEM_DEVICE))
+        return tuple(outs)
+
+    @property
+    def rgb(self) -> np.ndarray:
+        """the colour image [H, W, 3] uint8"""
+        return self._host("rgb")
+
+    @property
+    def theta(self) -> np.ndarray:
+        """(clipped z - z_min) / (z_max - z_min) of every pixel's point [H, W] float32; float32(z_min) where it is empty"""
+        return self._host("theta")
+
+    @property
+    def points_3d(self) -> np.ndarray:
+        """the point behind every pixel [H, W, 3] float32, zeros where it is empty (`points_3D`)"""
+        return self._host("points_3d")
+
+    @property
+    def indices(self) -> np.ndarray:
+        """the row behind every pixel [H, W] int32, -1 where it is empty (`pc_indices`)"""
+        return self._host("indices")
+
+    def build_image(self, pc: Array):
+        """What the reference's `build_image` returns: (uint8 [H, W, 3], {"points_3D": float32 [H, W, 3], "pc_indices": int64
+        [H, W]}), on the host."""
+        self.build(pc)
+        return self.rgb, {"points_3D": self.points_3d, "pc_indices": self.indices.astype(np.int64)}
 
 
 class IcpBatch:

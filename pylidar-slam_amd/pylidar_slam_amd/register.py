@@ -119,3 +119,55 @@ def install_kdtree():
         if held is not None and held is not kdtree.KDTree and getattr(held, "__module__", "").startswith("pykdtree"):
             setattr(mod, "KDTree", kdtree.KDTree)
     return kdtree
+
+
+class _DeviceElevationBuilder:
+    """The default builder of `install_elevation_image`: an `ElevationImage` with the settings of one reference object, on a
+    context shared by all of them, recreated with more room when a cloud has more rows than it takes."""
+    _ctx = None
+
+    def __init__(self, owner):
+        self.owner, self.image = owner, None
+
+    def build_image(self, pc):
+        from .engine import IcpContext, colormap_table
+        rows = int(pc.shape[0])
+        if self.image is None or rows > self.image.max_rows:
+            if _DeviceElevationBuilder._ctx is None:
+                _DeviceElevationBuilder._ctx = IcpContext()
+            if self.image is not None:
+                self.image.close()
+            o = self.owner
+            room = 1 << max(17, (rows - 1).bit_length())
+            self.image = _DeviceElevationBuilder._ctx.elevation_image(o.H, o.W, o.pixel_size, o.z_min, o.z_max, o.flip_axis,
+                                                                      colormap_table(o.color_map), room)
+        return self.image.build_image(pc)
+
+
+def install_elevation_image(factory=None):
+    """Assigns the reference's `ElevationImageRegistration` (slam/common/registration.py:179-241; the class exists only where
+    `cv2` does) a `build_image` that routes through a per-instance builder on the MI355X, so that its callers — the loop
+    closure, slam/loop_closure.py:294, and `ElevationImageInitialization`, slam/initialization.py:176 — rasterise on the device.
+    `factory(instance)` returns an object with `build_image(pc)`; the default builds an `engine.ElevationImage` from the
+    instance's H, W, pixel_size, z_min, z_max, flip_axis and color_map.  A builder is made again when one of those settings
+    changes.  Returns the patched class, or None where the reference does not define it."""
+    try:
+        import slam.common.registration as ref_registration
+    except ImportError:
+        return None
+    cls = getattr(ref_registration, "ElevationImageRegistration", None)
+    if cls is None:
+        return None
+    make = factory or _DeviceElevationBuilder
+
+    def build_image(self, pc):
+        key = (self.H, self.W, self.pixel_size, self.z_min, self.z_max, bool(self.flip_axis), id(self.color_map))
+        held = self.__dict__.get("_mi355x_elevation")
+        if held is None or held[0] != key:
+            held = (key, make(self))
+            self.__dict__["_mi355x_elevation"] = held
+        return held[1].build_image(pc)
+
+    build_image.__doc__ = "Builds an elevation image (on the MI355X: pylidar_slam_amd.register.install_elevation_image)"
+    cls.build_image = build_image
+    return cls
