@@ -134,7 +134,12 @@ int icp_synchronize(icp_ctx* ctx);
  *   "scan_poll_limit" n (2^20)      grid build (without "cell_lists"): polls of a predecessor tile's descriptor before a tile of the one-launch table
  *                                   scan computes its prefix from the table itself (a safeguard; tests set 0 to walk that path)
  *   "prune_guard" m (0.002)         searches scan neighbour cells whose box is within m metres of the best distance instead of
- *                                   pruning them (the gap of a pruned cell bounds the cache's L: a guard keeps L off the best)
+ *                                   pruning them (the gap of a pruned cell bounds the cache's L: a guard keeps L off the best).
+ *                                   Speed only: exactness does not rest on it.  Every box gap is taken short by 16 * 2^-24 *
+ *                                   (|coordinate| + (|cell offset| + 1) * cell edge), which covers the few ulp by which cell
+ *                                   membership (floorf(p / h)) and cell boxes (c * h) disagree; 0 gives the same bits
+ *                                   (tests/test_gpu_search_audit.py; before that audit 0 could return a neighbour micrometres
+ *                                   farther than the nearest, and the coarse level and knn_query, which have no guard, did)
  *   "refresh_at" n (2), "refresh_margin" m (2e-3)   in launch n, NN-cache entries with less slack than m are searched again
  *   "xcd_sectors" 0 | 1 (1)         the workgroups one XCD receives take one azimuth sector of the range image
  *   "lead_after_dense" 0 | 1 (1)    the first 512-query launch also solves the last 128-query one

@@ -66,10 +66,11 @@ __device__ inline bool knn_level_share(const GridView& g, float px, float py, fl
     if constexpr (NL == 1) return knn_level<KN>(g, px, py, pz, 0, max_rings, false, m);
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
     const float h = g.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     TopK<KN> t;
     knn_fill<KN>(t, sentinel);
     int start, count;
@@ -80,18 +81,18 @@ __device__ inline bool knn_level_share(const GridView& g, float px, float py, fl
         const unsigned long long cap = m.key[KN - 1];
         const float capd = key_d2(cap);
         for (int oz = -r; oz <= r; ++oz) {
-            const float gz = axis_gap(oz, fz, h);
+            const float gz = axis_gap(oz, fz, hs);
             const float gz2 = gz * gz;
             if (gz2 > fminf(t.kth(), capd)) continue;
             const int az = oz < 0 ? -oz : oz;
             for (int oy = -r; oy <= r; ++oy) {
-                const float gy = axis_gap(oy, fy, h);
+                const float gy = axis_gap(oy, fy, hs);
                 const float gyz2 = fmaf(gy, gy, gz2);
                 if (gyz2 > fminf(t.kth(), capd)) continue;
                 const int ay = oy < 0 ? -oy : oy;
                 const int step = ((az == r) || (ay == r)) ? 1 : 2 * r;
                 for (int ox = -r; ox <= r; ox += step) {
-                    const float gx = axis_gap(ox, fx, h);
+                    const float gx = axis_gap(ox, fx, hs);
                     if (fmaf(gx, gx, gyz2) > fminf(t.kth(), capd)) continue;
                     if (grid_lookup(g, cx + ox, cy + oy, cz + oz, start, count))
                         scan_cell_share<KN, NL>(g, start, count, sub, px, py, pz, cap, t);
@@ -99,7 +100,7 @@ __device__ inline bool knn_level_share(const GridView& g, float px, float py, fl
             }
         }
         knn_merge_share<KN, NL>(t, m, sub, sentinel);
-        const float bound = (float)r * h + edge;
+        const float bound = ring_bound(r, hs, edge);
         exact = m.kth() <= bound * bound * 0.999999f;
     }
     return exact;

@@ -65,34 +65,35 @@ __device__ inline bool knn_level(const GridView& g, float px, float py, float pz
                                  bool translate, TopK<KN>& t) {
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
     const float h = g.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     int start, count;
     if (first_ring == 0 && grid_lookup(g, cx, cy, cz, start, count)) scan_cell_knn<KN>(g, start, count, px, py, pz, t);
     bool exact = false;
     for (int r = first_ring < 1 ? 1 : first_ring; r <= max_rings && !exact; ++r) {
         for (int oz = -r; oz <= r; ++oz) {
-            const float gz = axis_gap(oz, fz, h);
+            const float gz = axis_gap(oz, fz, hs);
             const float gz2 = gz * gz;
             if (gz2 > t.kth()) continue;
             const int az = oz < 0 ? -oz : oz;
             for (int oy = -r; oy <= r; ++oy) {
-                const float gy = axis_gap(oy, fy, h);
+                const float gy = axis_gap(oy, fy, hs);
                 const float gyz2 = fmaf(gy, gy, gz2);
                 if (gyz2 > t.kth()) continue;
                 const int ay = oy < 0 ? -oy : oy;
                 const int step = ((az == r) || (ay == r)) ? 1 : 2 * r;
                 for (int ox = -r; ox <= r; ox += step) {
-                    const float gx = axis_gap(ox, fx, h);
+                    const float gx = axis_gap(ox, fx, hs);
                     if (fmaf(gx, gx, gyz2) > t.kth()) continue;
                     if (grid_lookup(g, cx + ox, cy + oy, cz + oz, start, count))
                         scan_cell_knn<KN>(g, start, count, px, py, pz, t);
                 }
             }
         }
-        const float bound = (float)r * h + edge;
+        const float bound = ring_bound(r, hs, edge);
         exact = t.kth() <= bound * bound * 0.999999f;
     }
     (void)translate;  // keys carry original indices: nothing to translate between levels

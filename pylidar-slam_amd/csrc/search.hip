@@ -7,6 +7,7 @@
 // Exactness: rings of cells (Chebyshev distance r around the query's cell) are visited until the best distance found
 // is provably not beaten by anything outside the visited block: best <= r*h + min_axis(min(f, h - f)), f = offset of
 // the query inside its cell.  Cells whose box is farther than the current best are skipped without a table probe.
+// Both distances are taken short by the few ulp by which cell membership and cell boxes disagree (search_device.h: cell_off).
 // Queries that exhaust `max_rings` fall back to an exhaustive scan, so the result is the exact NN for every input.
 // Distance ties are broken on the smaller original map index (the kd-tree's tie order is unspecified).
 #include <type_traits>
@@ -84,10 +85,11 @@ __device__ inline bool coop_rings(const GridView& lv, float px, float py, float 
                                   Best& b, int2* __restrict__ stack, int stride) {
     const int cx = cell_coord(px, lv.inv_h), cy = cell_coord(py, lv.inv_h), cz = cell_coord(pz, lv.inv_h);
     const float h = lv.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     for (int r = r_begin; r <= r_end; ++r) {
         int start, count;
         if (r == 0) {
@@ -104,7 +106,7 @@ __device__ inline bool coop_rings(const GridView& lv, float px, float py, float 
                     const int ox = c % side - r, oy = (c / side) % side - r, oz = c / (side * side) - r;
                     const int m = max(max(ox < 0 ? -ox : ox, oy < 0 ? -oy : oy), oz < 0 ? -oz : oz);
                     if (m < r) continue;  // interior: visited by the previous rings
-                    const float gx = axis_gap(ox, fx, h), gy = axis_gap(oy, fy, h), gz = axis_gap(oz, fz, h);
+                    const float gx = axis_gap(ox, fx, hs), gy = axis_gap(oy, fy, hs), gz = axis_gap(oz, fz, hs);
                     const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
                     if (gap2 > b.d2) {
                         b.second = fminf(b.second, gap2);  // every point of a pruned cell is at least that far
@@ -132,7 +134,7 @@ __device__ inline bool coop_rings(const GridView& lv, float px, float py, float 
             }
         }
         group_min4(b);
-        const float bound = (float)r * h + edge;
+        const float bound = ring_bound(r, hs, edge);
         if (b.d2 <= bound * bound * 0.999999f) {
             b.second = fminf(b.second, bound * bound * 0.999999f);  // nothing outside the visited block is closer
             return true;
@@ -166,10 +168,11 @@ __device__ inline Near3 search_rows_group(const GridView& g, float px, float py,
     float r2 = seed_d2;
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
     const float h = g.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     // own cell: the entry of the first slot and — rows are indexed by slot — this lane's 7 row entries are fetched
     // together (a first-probe hit is the common case; the speculative row is simply reloaded after a collision)
     const unsigned long long key = pack_cell(cx, cy, cz);
@@ -202,8 +205,8 @@ __device__ inline Near3 search_rows_group(const GridView& g, float px, float py,
         for (int k = 0; k < 7; ++k) {
             const int c = sub * 7 + k;
             if (c == 13 || c >= 27 || cell[k].y <= 0) continue;  // own cell done above; entry 27 is padding
-            const float gx = axis_gap(c % 3 - 1, fx, h), gy = axis_gap((c / 3) % 3 - 1, fy, h),
-                        gz = axis_gap(c / 9 - 1, fz, h);
+            const float gx = axis_gap(c % 3 - 1, fx, hs), gy = axis_gap((c / 3) % 3 - 1, fy, hs),
+                        gz = axis_gap(c / 9 - 1, fz, hs);
             const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
             if (gap2 > prune2) {
                 b.second = fminf(b.second, gap2);  // every point of a pruned cell is at least that far
@@ -301,8 +304,8 @@ __device__ inline Near3 search_rows_group(const GridView& g, float px, float py,
                 ++ci;
                 const int c = (int)((unsigned)nx.y >> 24);
                 // the best may have shrunk since the cell was queued
-                const float gx = axis_gap(c % 3 - 1, fx, h), gy = axis_gap((c / 3) % 3 - 1, fy, h),
-                            gz = axis_gap(c / 9 - 1, fz, h);
+                const float gx = axis_gap(c % 3 - 1, fx, hs), gy = axis_gap((c / 3) % 3 - 1, fy, hs),
+                            gz = axis_gap(c / 9 - 1, fz, hs);
                 const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
                 if (gap2 > prune2) {
                     b.second = fminf(b.second, gap2);
@@ -327,7 +330,7 @@ __device__ inline Near3 search_rows_group(const GridView& g, float px, float py,
         for (int c0 = sub; c0 < 26; c0 += 4) {
             const int c = c0 + (c0 >= 13 ? 1 : 0);
             const int ox = c % 3 - 1, oy = (c / 3) % 3 - 1, oz = c / 9 - 1;
-            const float gx = axis_gap(ox, fx, h), gy = axis_gap(oy, fy, h), gz = axis_gap(oz, fz, h);
+            const float gx = axis_gap(ox, fx, hs), gy = axis_gap(oy, fy, hs), gz = axis_gap(oz, fz, hs);
             const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
             if (gap2 > fminf(r2, b.d2)) {
                 b.second = fminf(b.second, gap2);
@@ -339,7 +342,7 @@ __device__ inline Near3 search_rows_group(const GridView& g, float px, float py,
         }
         r2 = fminf(r2, quad_min(b.d2));
     }
-    float bound = h + edge;
+    float bound = ring_bound(1, hs, edge);
     bool resolved = r2 <= bound * bound * 0.999999f;  // group-uniform: r2 is shared
     if (g.dbg && sub == 0) atomicAdd(&g.dbg[resolved ? 0 : 1], 1);
     if (g.dbg && sub == 0 && e.key != key) atomicAdd(&g.dbg[5], 1);
@@ -529,10 +532,11 @@ __device__ __forceinline__ bool far_rings_w(const GridView& lv, float px, float 
                                    int2* __restrict__ col0, int stride) {
     const int cx = cell_coord(px, lv.inv_h), cy = cell_coord(py, lv.inv_h), cz = cell_coord(pz, lv.inv_h);
     const float h = lv.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     for (int r = r_begin; r <= r_end; ++r) {
         const int side = 2 * r + 1, total = side * side * side;
         for (int c0 = 0; c0 < total; c0 += 7 * W) {  // group-uniform
@@ -544,7 +548,7 @@ __device__ __forceinline__ bool far_rings_w(const GridView& lv, float px, float 
                 const int ox = c % side - r, oy = (c / side) % side - r, oz = c / (side * side) - r;
                 const int m = max(max(ox < 0 ? -ox : ox, oy < 0 ? -oy : oy), oz < 0 ? -oz : oz);
                 if (m < r && r > r_begin) continue;  // interior: visited by the previous rings
-                const float gx = axis_gap(ox, fx, h), gy = axis_gap(oy, fy, h), gz = axis_gap(oz, fz, h);
+                const float gx = axis_gap(ox, fx, hs), gy = axis_gap(oy, fy, hs), gz = axis_gap(oz, fz, hs);
                 const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
                 if (gap2 > b.d2) {
                     b.second = fminf(b.second, gap2);  // every point of a pruned cell is at least that far
@@ -560,7 +564,7 @@ __device__ __forceinline__ bool far_rings_w(const GridView& lv, float px, float 
             walk_found_w<W>(lv, found, col0, stride, sub, px, py, pz, b);
         }
         group_min_w<W>(b);
-        const float bound = (float)r * h + edge;
+        const float bound = ring_bound(r, hs, edge);
         if (b.d2 <= bound * bound * 0.999999f) {
             b.second = fminf(b.second, bound * bound * 0.999999f);  // nothing outside the visited block is closer
             return true;
@@ -686,10 +690,11 @@ __device__ inline bool search_rows_wave(const GridView& g, float px, float py, f
     if (third) third->pos = -1;
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
     const float h = g.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     const unsigned long long key = pack_cell(cx, cy, cz);
     unsigned int slot = hash_cell(key) & g.mask;
     const int c = min(lane, 27);  // entry 27 is the (0, 0) padding
@@ -720,7 +725,7 @@ __device__ inline bool search_rows_wave(const GridView& g, float px, float py, f
     int cnt = 0;
     float pruned_gap = INFINITY;  // this lane's pruned cell (if any): all its points are at least that far
     if (lane < 27) {
-        const float gx = axis_gap(c % 3 - 1, fx, h), gy = axis_gap((c / 3) % 3 - 1, fy, h), gz = axis_gap(c / 9 - 1, fz, h);
+        const float gx = axis_gap(c % 3 - 1, fx, hs), gy = axis_gap((c / 3) % 3 - 1, fy, hs), gz = axis_gap(c / 9 - 1, fz, hs);
         const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
         cnt = rc.y;
         // (pruned only when the box is farther than the seed by `prune_guard`: the gap of a pruned cell bounds L, and a
@@ -765,7 +770,7 @@ __device__ inline bool search_rows_wave(const GridView& g, float px, float py, f
         if (pb >= 0) consider(qb, pb, px, py, pz, b);
     }
     wave_min64(b);
-    float bound = h + edge;
+    float bound = ring_bound(1, hs, edge);
     if (b.d2 <= bound * bound * 0.999999f) {
         b.second = fminf(b.second, bound * bound * 0.999999f);  // nothing outside the 27-cell block is closer
         if (runner && total <= 128 && b.pos >= 0) {
@@ -810,7 +815,7 @@ __device__ inline bool search_rows_wave(const GridView& g, float px, float py, f
     for (int s5 = lane; s5 < 125; s5 += 64) {
         const int ox = s5 % 5 - 2, oy = (s5 / 5) % 5 - 2, oz = s5 / 25 - 2;
         if (max(max(ox < 0 ? -ox : ox, oy < 0 ? -oy : oy), oz < 0 ? -oz : oz) < 2) continue;  // rings 0 and 1: done
-        const float gx = axis_gap(ox, fx, h), gy = axis_gap(oy, fy, h), gz = axis_gap(oz, fz, h);
+        const float gx = axis_gap(ox, fx, hs), gy = axis_gap(oy, fy, hs), gz = axis_gap(oz, fz, hs);
         const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
         if (gap2 > b.d2) {
             b.second = fminf(b.second, gap2);
@@ -821,7 +826,7 @@ __device__ inline bool search_rows_wave(const GridView& g, float px, float py, f
             for (int k = start; k < start + count; ++k) consider(g.pts[k], k, px, py, pz, b);  // rare: kept small
     }
     wave_min64(b);
-    bound = 2.f * h + edge;
+    bound = ring_bound(2, hs, edge);
     if (!(b.d2 <= bound * bound * 0.999999f)) return false;
     b.second = fminf(b.second, bound * bound * 0.999999f);
     return true;
@@ -968,14 +973,16 @@ __device__ inline bool search_ball_lane(const GridView& g, float px, float py, f
     seed_pos = -1;
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
     const float h = g.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
     // the nearer face of every axis: only a ball that reaches it leaves the cell on that side
-    const bool lx = fx < h - fx, ly = fy < h - fy, lz = fz < h - fz;
-    const float nx = lx ? fx : h - fx, ny = ly ? fy : h - fy, nz = lz ? fz : h - fz;
-    // every cell outside the 2x2x2 block on the nearer sides is at least that far
-    const float outer = h - fmaxf(nx, fmaxf(ny, nz));
+    // (distances short by the slack of cell_off, clamped at 0: search_device.h)
+    const bool lx = fx.lo < fx.hi, ly = fy.lo < fy.hi, lz = fz.lo < fz.hi;
+    const float nx = fmaxf(lx ? fx.lo : fx.hi, 0.f), ny = fmaxf(ly ? fy.lo : fy.hi, 0.f), nz = fmaxf(lz ? fz.lo : fz.hi, 0.f);
+    // every cell outside the 2x2x2 block on the nearer sides is at least that far: the farther face of some axis
+    const float outer = fmaxf(fminf(lx ? fx.hi : fx.lo, fminf(ly ? fy.hi : fy.lo, lz ? fz.hi : fz.lo)), 0.f);
     const unsigned long long key = pack_cell(cx, cy, cz);
     unsigned int slot = hash_cell(key) & g.mask;
     const int o1 = lx ? -1 : 1, o2 = ly ? -3 : 3, o4 = lz ? -9 : 9;
@@ -1042,7 +1049,7 @@ __device__ inline bool search_ball_lane(const GridView& g, float px, float py, f
     // a ball that leaves the 2x2x2 block but stays inside the 3x3x3 one (round 6: a query half a metre from its surface in
     // 0.5 m cells — a sixth of the scan when the initial guess is that far off): every cell of the 26 whose box the ball
     // reaches, from the own cell's row or, where the own cell is empty, by hashed probes seven at a time
-    const float outer3 = h + fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float outer3 = ring_bound(1, hs, cell_edge(fx, fy, fz));
     bool block3 = !inside && through_empty && R < outer3;
     float Lb2 = block3 ? outer3 * outer3 : outer * outer;
     int ns = 0, total = cum0;
@@ -1051,7 +1058,7 @@ __device__ inline bool search_ball_lane(const GridView& g, float px, float py, f
 #pragma unroll
         for (int idx = 0; idx < 27; ++idx) {
             if (idx == 13) continue;
-            const float gx = axis_gap(idx % 3 - 1, fx, h), gy = axis_gap((idx / 3) % 3 - 1, fy, h), gz = axis_gap(idx / 9 - 1, fz, h);
+            const float gx = axis_gap(idx % 3 - 1, fx, hs), gy = axis_gap((idx / 3) % 3 - 1, fy, hs), gz = axis_gap(idx / 9 - 1, fz, hs);
             const float gap2 = fmaf(gx, gx, fmaf(gy, gy, gz * gz));
             if (gap2 > R2) Lb2 = fminf(Lb2, gap2);  // (every point such a cell may hold is at least that far)
             else surv |= 1u << idx;
@@ -2594,10 +2601,11 @@ __device__ inline bool wave_knn_rings(const GridView& lv, float px, float py, fl
                                       float limit, TopK<KN>& m, int* __restrict__ wl) {
     const int cx = cell_coord(px, lv.inv_h), cy = cell_coord(py, lv.inv_h), cz = cell_coord(pz, lv.inv_h);
     const float h = lv.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     for (int r = r_begin; r <= r_end; ++r) {
         TopK<KN> t;
         if (lane == 0) {
@@ -2614,7 +2622,7 @@ __device__ inline bool wave_knn_rings(const GridView& lv, float px, float py, fl
                 const int ox = c % side - r, oy = (c / side) % side - r, oz = c / (side * side) - r;
                 const int mx = max(max(ox < 0 ? -ox : ox, oy < 0 ? -oy : oy), oz < 0 ? -oz : oz);
                 if (mx == r) {  // the shell only: the interior belongs to the previous rings
-                    const float gx = axis_gap(ox, fx, h), gy = axis_gap(oy, fy, h), gz = axis_gap(oz, fz, h);
+                    const float gx = axis_gap(ox, fx, hs), gy = axis_gap(oy, fy, hs), gz = axis_gap(oz, fz, hs);
                     if (!(fmaf(gx, gx, fmaf(gy, gy, gz * gz)) > kth) &&
                         !grid_lookup(lv, cx + ox, cy + oy, cz + oz, start, count))
                         count = 0;
@@ -2658,7 +2666,7 @@ __device__ inline bool wave_knn_rings(const GridView& lv, float px, float py, fl
             __builtin_amdgcn_wave_barrier();  // the next round overwrites wl
         }
         merge_group<KN, 64>(t, m);
-        const float bound = (float)r * h + edge;
+        const float bound = ring_bound(r, hs, edge);
         if (m.kth() <= bound * bound * 0.999999f) return true;
     }
     return false;
@@ -2680,10 +2688,11 @@ __device__ inline bool estimate_cov(const GridView& g, int s, int sub, float* __
     t.init();
     const float h = g.h;
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     const int2* __restrict__ r = g.rows + (size_t)g.row_of_pos[s] * ROW_STRIDE;
     const int2 own = r[13];
     constexpr int CPL = ROW_STRIDE / NL;  // row entries per lane (entry 27 is padding)
@@ -2722,8 +2731,8 @@ __device__ inline bool estimate_cov(const GridView& g, int s, int sub, float* __
                 const int2 nx = stack[ci * stride];
                 ++ci;
                 const int c = (int)((unsigned)nx.y >> 24);
-                const float gx = axis_gap(c % 3 - 1, fx, h), gy = axis_gap((c / 3) % 3 - 1, fy, h),
-                            gz = axis_gap(c / 9 - 1, fz, h);
+                const float gx = axis_gap(c % 3 - 1, fx, hs), gy = axis_gap((c / 3) % 3 - 1, fy, hs),
+                            gz = axis_gap(c / 9 - 1, fz, hs);
                 if (fmaf(gx, gx, fmaf(gy, gy, gz * gz)) > t.kth()) continue;
                 st = nx.x;
                 cnt = nx.y & 0xffffff;
@@ -2740,7 +2749,7 @@ __device__ inline bool estimate_cov(const GridView& g, int s, int sub, float* __
         }
     }
     merge_group<KN, NL>(t, m);
-    const float bound1 = h + edge;
+    const float bound1 = ring_bound(1, hs, edge);
     const bool exact = m.kth() <= bound1 * bound1 * 0.999999f;  // group-uniform: m is shared
     if (exact && sub == 0) neighbourhood_cov<KN>(g, px, py, pz, m, cov);
     return exact;
@@ -2775,10 +2784,11 @@ __device__ inline bool estimate_cov_hood(const GridView& g, int s, int sub, floa
     const float px = P.x, py = P.y, pz = P.z;
     const float h = g.h;
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     const int2 hh = g.rows[(size_t)g.row_of_pos[s] * ROW_STRIDE + 27];
     const float4* __restrict__ H = g.hood + hh.x;
     const int n = hh.y;
@@ -2811,7 +2821,7 @@ __device__ inline bool estimate_cov_hood(const GridView& g, int s, int sub, floa
 #pragma unroll
         for (int i = 0; i < KN; ++i) T = fmaxf(T, fminf(E[i], quad_xor<2>(E[KN - 1 - i])));
     }
-    const float bound = h + edge;
+    const float bound = ring_bound(1, hs, edge);
     if (!(T <= bound * bound * 0.999999f)) return false;  // group-uniform (T is): ring 1 does not certify the KN-th neighbour
     if (n > 65535) return false;                          // (the notes below are 16-bit list positions)
     // ---- pass 2: who is in
@@ -3151,10 +3161,11 @@ __device__ inline bool cov_hood_pair(const GridView& g, int s, int sub, float* _
     const float px = P.x, py = P.y, pz = P.z;
     const float h = g.h;
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     const int2 hh = g.rows[(size_t)g.row_of_pos[s] * ROW_STRIDE + 27];
     const int n = hh.y, n4 = (n + 3) & ~3;  // (runs are padded to whole groups of four with points at +inf)
     if (n < KN || n4 > (int)HOOD_JMASK + 1) return false;  // pair-uniform
@@ -3191,7 +3202,7 @@ __device__ inline bool cov_hood_pair(const GridView& g, int s, int sub, float* _
     for (int i = 0; i <= KN; ++i) m.insert(min(t.k[i], (unsigned)quad_xor<1>((int)t.k[KN - i])));
     if (m.k[KN - 1] >= 0x7f800000u) return false;  // fewer than KN finite distances
     // ring 1 certifies the KN-th neighbour ...
-    const float bound = h + edge;
+    const float bound = ring_bound(1, hs, edge);
     if (!(__uint_as_float(m.k[KN - 1] | HOOD_JMASK) <= bound * bound * 0.999999f)) return false;
     // ... and the keys name the KN nearest when everybody else is a whole truncation step farther
     if ((m.k[KN] & ~HOOD_JMASK) == (m.k[KN - 1] & ~HOOD_JMASK)) return false;
@@ -3228,10 +3239,11 @@ __device__ inline void normal_of_straggler(const GridView& g, int ps, int lane, 
     // (round 6) three stragglers in ten are points of DENSE cells whose KN-th and KN + 1-th neighbours the pair pass's
     // truncated keys could not tell apart: the exact keys settle them inside ring 1, no ring 2
     const float h = g.h;
-    const float fx = fminf(fmaxf(P.x - (float)cell_coord(P.x, g.inv_h) * h, 0.f), h);
-    const float fy = fminf(fmaxf(P.y - (float)cell_coord(P.y, g.inv_h) * h, 0.f), h);
-    const float fz = fminf(fmaxf(P.z - (float)cell_coord(P.z, g.inv_h) * h, 0.f), h);
-    const float bound1 = h + fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(P.x, cell_coord(P.x, g.inv_h), h);
+    const CellOff fy = cell_off(P.y, cell_coord(P.y, g.inv_h), h);
+    const CellOff fz = cell_off(P.z, cell_coord(P.z, g.inv_h), h);
+    const float bound1 = ring_bound(1, hs, cell_edge(fx, fy, fz));
     if (m.kth() <= bound1 * bound1 * 0.999999f) {  // (wave-uniform: m is the same in every lane)
         if (lane == 0) neighbourhood_cov<KN>(g, P.x, P.y, P.z, m, wcov);
     } else {
@@ -3396,10 +3408,11 @@ __device__ inline bool cov_ring2_row16(const GridView& g, int ps, int sub, float
     const float px = P.x, py = P.y, pz = P.z;
     const float h = g.h;
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     const int2 hh = g.rows[(size_t)g.row_of_pos[ps] * ROW_STRIDE + 27];
     if (hh.y > 2048) return false;  // (row-uniform) the wave path
     if (g.dbg && sub == 0) atomicAdd(&g.dbg[7], 1);  // ("knn: beyond ring 1")
@@ -3420,7 +3433,7 @@ __device__ inline bool cov_ring2_row16(const GridView& g, int ps, int sub, float
     merge_group<KN, 16>(t, m);
     // most stragglers are points of DENSE cells whose KN-th and KN + 1-th neighbours the pair pass's truncated 32-bit keys
     // could not tell apart: the exact keys settle them inside ring 1
-    const float bound1 = h + edge;
+    const float bound1 = ring_bound(1, hs, edge);
     if (!(m.kth() <= bound1 * bound1 * 0.999999f)) {  // (row-uniform: m is the same in the sixteen lanes)
         // the shell of ring 2: the cells whose box the KN-th distance so far reaches, seven hashed probes per lane in flight
         const float kth = m.kth();
@@ -3431,7 +3444,7 @@ __device__ inline bool cov_ring2_row16(const GridView& g, int ps, int sub, float
             if (sub + 16 * k < 98) {
                 int ox, oy, oz;
                 ring2_shell_cell(sub + 16 * k, ox, oy, oz);
-                const float gx = axis_gap(ox, fx, h), gy = axis_gap(oy, fy, h), gz = axis_gap(oz, fz, h);
+                const float gx = axis_gap(ox, fx, hs), gy = axis_gap(oy, fy, hs), gz = axis_gap(oz, fz, hs);
                 if (!(fmaf(gx, gx, fmaf(gy, gy, gz * gz)) > kth)) want |= 1 << k;
             }
         }
@@ -3450,7 +3463,7 @@ __device__ inline bool cov_ring2_row16(const GridView& g, int ps, int sub, float
             if (found[k].y > 0) scan_cell_knn<KN>(g, found[k].x, found[k].y, px, py, pz, t);
         merge_group<KN, 16>(t, m);
         // ring 2 certifies the KN-th neighbour (finite: the map holds KN points within its reach)
-        const float bound = 2.0f * h + edge;
+        const float bound = ring_bound(2, hs, edge);
         if (!(m.kth() <= bound * bound * 0.999999f)) return false;
     }
     // the covariance (neighbourhood_cov's terms: members 1 .. KN - 1, the nearest — the point itself or a twin — dropped): one

@@ -92,11 +92,38 @@ __device__ inline bool grid_lookup(const GridView& g, int cx, int cy, int cz, in
     }
 }
 
-// squared distance from the query (offset f inside its own cell, per axis) to the box of the cell at offset o
-__device__ inline float axis_gap(int o, float f, float h) {
-    if (o == 0) return 0.f;
-    return o < 0 ? f + (float)(-o - 1) * h : (h - f) + (float)(o - 1) * h;
+// Membership and boxes disagree.  A point belongs to the cell floorf(p * inv_h) (cell_coord), the search takes the box of
+// cell c to start at (float)c * h: for an h that is no power of two a point can sit in cell k and lie a few ulp of its
+// coordinate below (float)k * h, so that the gap to "its" box exceeds its distance.  Every gap that prunes a cell, ends a
+// ring search or bounds the NN cache is therefore taken SHORT by GAP_SLACK * (|p| + (|o| + 1) * h), clamped at 0 — sixteen
+// units of 2^-24 where the roundings of inv_h, p * inv_h, c * h, p - c * h, h - f, (|o| - 1) * h, the sum and the squares add
+// up to fewer than twelve (DESIGN.md section 4 has the derivation).  CellOff carries the two distances of one axis, to the
+// lower and to the upper face of the own cell's box, already short by GAP_SLACK * (|p| + 2 h); slack_h(h) = h - GAP_SLACK * h
+// is what every further cell adds.
+static constexpr float GAP_SLACK = 16.0f / 16777216.0f;
+struct CellOff {
+    float lo, hi;
+};
+__device__ inline float slack_h(float h) { return h - GAP_SLACK * h; }
+__device__ inline CellOff cell_off(float p, int c, float h) {
+    const float f = fminf(fmaxf(p - (float)c * h, 0.f), h);
+    const float s = GAP_SLACK * (fabsf(p) + 2.f * h);
+    CellOff o;
+    o.lo = f - s;
+    o.hi = (h - f) - s;
+    return o;
 }
+// distance from the query to the box of the cell at offset o on one axis, short by the slack (hs = slack_h(h))
+__device__ inline float axis_gap(int o, CellOff f, float hs) {
+    if (o == 0) return 0.f;
+    return fmaxf(o < 0 ? f.lo + (float)(-o - 1) * hs : f.hi + (float)(o - 1) * hs, 0.f);
+}
+// the smallest of the six (may be negative: ring_bound clamps)
+__device__ inline float cell_edge(CellOff x, CellOff y, CellOff z) {
+    return fminf(fminf(fminf(x.lo, x.hi), fminf(y.lo, y.hi)), fminf(z.lo, z.hi));
+}
+// nothing outside the block of rings <= r is closer than this
+__device__ inline float ring_bound(int r, float hs, float edge) { return fmaxf((float)r * hs + edge, 0.f); }
 
 // `skip` (optional): an original index this lane must not take — the seed of a 4-lane search belongs to lane 0 alone
 // (the lanes keep local bests until the end: the same point in two of them would waste a place of the candidate set)
@@ -140,20 +167,21 @@ __device__ inline bool nearest_in_level(const GridView& g, float px, float py, f
     b.second = 0.f;  // the generic path does not feed the NN cache
     const int cx = cell_coord(px, g.inv_h), cy = cell_coord(py, g.inv_h), cz = cell_coord(pz, g.inv_h);
     const float h = g.h;
-    const float fx = fminf(fmaxf(px - (float)cx * h, 0.f), h);
-    const float fy = fminf(fmaxf(py - (float)cy * h, 0.f), h);
-    const float fz = fminf(fmaxf(pz - (float)cz * h, 0.f), h);
-    const float edge = fminf(fminf(fminf(fx, h - fx), fminf(fy, h - fy)), fminf(fz, h - fz));
+    const float hs = slack_h(h);
+    const CellOff fx = cell_off(px, cx, h);
+    const CellOff fy = cell_off(py, cy, h);
+    const CellOff fz = cell_off(pz, cz, h);
+    const float edge = cell_edge(fx, fy, fz);
     int start, count;
     if (grid_lookup(g, cx, cy, cz, start, count)) scan_cell_1nn(g, start, count, px, py, pz, b);
     for (int r = 1; r <= max_rings; ++r) {
         for (int oz = -r; oz <= r; ++oz) {
-            const float gz = axis_gap(oz, fz, h);
+            const float gz = axis_gap(oz, fz, hs);
             const float gz2 = gz * gz;
             if (gz2 > b.d2) continue;
             const int az = oz < 0 ? -oz : oz;
             for (int oy = -r; oy <= r; ++oy) {
-                const float gy = axis_gap(oy, fy, h);
+                const float gy = axis_gap(oy, fy, hs);
                 const float gyz2 = fmaf(gy, gy, gz2);
                 if (gyz2 > b.d2) continue;
                 const int ay = oy < 0 ? -oy : oy;
@@ -161,14 +189,14 @@ __device__ inline bool nearest_in_level(const GridView& g, float px, float py, f
                 // on the shell in y/z every x is visited, otherwise only x = -r and x = +r
                 const int step = shell_yz ? 1 : 2 * r;
                 for (int ox = -r; ox <= r; ox += step) {
-                    const float gx = axis_gap(ox, fx, h);
+                    const float gx = axis_gap(ox, fx, hs);
                     if (fmaf(gx, gx, gyz2) > b.d2) continue;
                     if (grid_lookup(g, cx + ox, cy + oy, cz + oz, start, count))
                         scan_cell_1nn(g, start, count, px, py, pz, b);
                 }
             }
         }
-        const float bound = (float)r * h + edge;
+        const float bound = ring_bound(r, hs, edge);
         if (b.d2 <= bound * bound * 0.999999f) return true;
     }
     return false;
