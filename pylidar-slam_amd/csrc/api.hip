@@ -721,7 +721,7 @@ int icp_distort(icp_ctx* ctx, const float* xyz, const double* timestamps, int64_
 // ---- time stamps from the azimuth ---------------------------------------------------------------------------------------
 // a frame launched on the context (by itself or by a batch) and not yet ended
 static bool frame_in_flight(const icp_ctx* ctx) {
-    return (ctx->frame && ctx->frame->launched) || (ctx->pframe && ctx->pframe->launched);
+    return (ctx->frame && ctx->frame->seq.launched) || (ctx->pframe && ctx->pframe->seq.launched);
 }
 
 // What icp_estimate_timestamps / icp_kitti360_prepare refuse.  They stage into scratch a registration and a frame use (the

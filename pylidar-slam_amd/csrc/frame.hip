@@ -1,9 +1,11 @@
 // One call per odometry frame: icp_odometry_init / icp_frame_launch / icp_frame_end (include/icp_mi355x.h).
 // ICPFrameToModel.do_process_next_frame (slam/odometry/icp_odometry.py:157-246) composed from the entry points of api.hip in
 // the order pylidar_slam_amd/odometry.py::MI355XICPFrameToModel issues them; host code only — every launch is one of theirs.
+// Also the steps of a frame that do not depend on the map (frame_loop.h): the upload, the preprocessing chain, the copy-out,
+// a pending frame dropped, frame 0's end, the registration collected, the key-frame outcome applied, odometry_pc delivered —
+// the projective frame calls (pmap_frame.hip) and the batched ones (batch_frame.hip) go through the same functions.
 #include <string.h>
 
-#include "frame_keyframe.h"
 #include "frame_loop.h"
 #include "icp_internal.h"
 
@@ -24,23 +26,78 @@ int frame_refusals(icp_ctx* ctx, const char* who) {
     return ICP_OK;
 }
 
-// a frame launched and never ended: its registration is collected and dropped, its copy waited for
-void frame_drop_pending(icp_ctx* ctx, icp_frame_loop* f) {
-    if (!f->launched) return;
-    if (f->registered && ctx->result_pending()) {
-        icp_register_result r;
-        (void)icp_register_end(ctx, &r, nullptr, nullptr);
-    }
-    if (f->copy_started) (void)hipEventSynchronize(f->copy_done);
-    f->copy_started = false;
-    f->launched = f->registered = false;
-}
-
 }  // namespace
 
 namespace icp {
 
-// ---- shared with the projective frame calls (pmap_frame.hip): frame_loop.h
+// ---- the steps shared with the projective frame calls (pmap_frame.hip) and the batched ones: frame_loop.h
+void frame_drop_pending(icp_ctx* ctx, icp_frame_seq* s, icp_frame_io* io) {
+    if (!s->launched) return;
+    if (s->registered && ctx->result_pending()) {
+        icp_register_result r;
+        (void)icp_register_end(ctx, &r, nullptr, nullptr);
+    }
+    if (io->copy_started) (void)hipEventSynchronize(io->copy_done);
+    io->copy_started = false;
+    s->launched = s->registered = false;
+}
+
+int frame_end_first(icp_ctx* ctx, icp_frame_seq* s, const icp_frame_io* io, int64_t inserted, bool wait_count,
+                    icp_frame_result* result) {
+    if (wait_count && s->sampled) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the grid sample's count)
+    pose_identity(result->reg.pose);
+    result->key_frame = 1;
+    result->inserted = inserted;
+    result->samples = s->sampled ? (int64_t)*io->pin_count : s->n;
+    s->launched = false;
+    s->index += 1;
+    return ICP_OK;
+}
+
+int frame_collect(icp_ctx* ctx, icp_frame_seq* s, icp_frame_io* io, icp_frame_result* result, double* loss_per_iter_out,
+                  float* dx_per_iter_out) {
+    const int rc = icp_register_end(ctx, &result->reg, loss_per_iter_out, dx_per_iter_out);
+    if (io->copy_started) ICP_HIP(ctx, hipEventSynchronize(io->copy_done));
+    result->samples = s->sampled && io->copy_started ? (int64_t)*io->pin_count : s->n;
+    if (rc) {
+        s->launched = s->registered = false;
+        io->copy_started = false;
+    }
+    return rc;
+}
+
+void frame_advance(icp_frame_seq* s, const KeyFrameTest& t, const float pose[16]) {
+    if (t.key_frame) pose_identity(s->delta);
+    else memcpy(s->delta, t.new_delta, sizeof(s->delta));
+    memcpy(s->last_pose, pose, sizeof(s->last_pose));
+    s->index += 1;
+}
+
+int frame_deliver(icp_ctx* ctx, const char* who, const icp_frame_seq* s, const icp_frame_io* io, bool copied, bool stage_late,
+                  const float* rows, int mode, float* odometry_pc_out, int64_t cap, int64_t* rows_out, int out_mem) {
+    int rc;
+    if (stage_late) {  // (not staged in front of the registration: compacted now)
+        if ((rc = icp_map_stage_cloud(ctx, rows, s->n, ICP_MEM_DEVICE, mode))) return rc;
+        ICP_HIP(ctx, hipEventSynchronize(ctx->staged_event));
+    }
+    const int64_t valid = s->n > 0 && (s->staged || odometry_pc_out) ? (int64_t)*ctx->staged_count_host : 0;
+    if (rows_out) *rows_out = valid;
+    if (!odometry_pc_out) return ICP_OK;
+    if (valid > cap)
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT,
+                    (std::string(who) + ": odometry_pc_out holds fewer rows than the frame has (count in *rows_out)").c_str());
+    if (valid > 0 && out_mem == ICP_MEM_HOST && copied) {
+        memcpy(odometry_pc_out, io->pin_out, (size_t)valid * 12);
+    } else if (valid > 0) {
+        // (not copied ahead, or a device buffer: behind the map update just enqueued, which reads the staged rows and
+        // leaves them as they are)
+        ICP_HIP(ctx, hipMemcpyAsync(odometry_pc_out, ctx->staged_xyz.ptr, (size_t)valid * 12,
+                                    out_mem == ICP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+        if (out_mem == ICP_MEM_HOST) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return ICP_OK;
+}
+
 int pinned_reserve(icp_ctx* ctx, void** ptr, size_t* have, size_t need) {
     if (*ptr && *have >= need) return ICP_OK;
     if (*ptr) ICP_HIP(ctx, hipHostFree(*ptr));
@@ -53,7 +110,7 @@ int pinned_reserve(icp_ctx* ctx, void** ptr, size_t* have, size_t need) {
 }
 
 // host rows (and timestamps) -> pinned buffer -> the next device slot, on the upload stream; the context's stream waits
-int frame_upload(icp_ctx* ctx, icp_frame_loop* f, const float* xyz, const double* ts, int64_t n, const float** rows_out,
+int frame_upload(icp_ctx* ctx, icp_frame_io* f, const float* xyz, const double* ts, int64_t n, const float** rows_out,
                  const double** ts_out) {
     const size_t row_bytes = ((size_t)n * 12 + 7) & ~(size_t)7;  // (the timestamps behind the rows, 8-byte aligned)
     const size_t bytes = row_bytes + (ts ? (size_t)n * 8 : 0);
@@ -83,9 +140,9 @@ int frame_upload(icp_ctx* ctx, icp_frame_loop* f, const float* xyz, const double
     return ICP_OK;
 }
 
-// de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126) of device rows, into the loop's
+// de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126) of device rows, into the io
 // buffers; guess = NULL: no de-skew.  *rows_out: the rows the frame goes on with (the input itself when nothing applies)
-int frame_preprocess_device(icp_ctx* ctx, icp_frame_loop* f, double voxel_size, const float* rows, int64_t n, const double* ts,
+int frame_preprocess_device(icp_ctx* ctx, icp_frame_io* f, double voxel_size, const float* rows, int64_t n, const double* ts,
                             const float* guess, const float** rows_out, bool* sampled_out) {
     int rc;
     const bool skew = n > 0 && ts != nullptr && guess != nullptr;
@@ -120,7 +177,7 @@ int frame_preprocess_device(icp_ctx* ctx, icp_frame_loop* f, double voxel_size, 
 
 // the staged rows (and the grid sample's count) towards pinned memory, beside the registration: behind the staging (its
 // event), on a stream of the loop's own
-int frame_copy_start(icp_ctx* ctx, icp_frame_loop* f, bool sample, bool cloud, int64_t n) {
+int frame_copy_start(icp_ctx* ctx, icp_frame_io* f, bool sample, bool cloud, int64_t n) {
     int rc;
     if (!f->copy_stream) ICP_HIP(ctx, hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking));
     if (!f->copy_done) ICP_HIP(ctx, hipEventCreateWithFlags(&f->copy_done, hipEventDisableTiming));
@@ -137,7 +194,7 @@ int frame_copy_start(icp_ctx* ctx, icp_frame_loop* f, bool sample, bool cloud, i
     return ICP_OK;
 }
 
-void frame_buffers_release(icp_frame_loop* f) {
+void frame_buffers_release(icp_frame_io* f) {
     DeviceBuffer* bufs[] = {&f->slot[0], &f->slot[1], &f->skew64, &f->samp64, &f->samp32, &f->vmap, &f->rows, &f->count};
     for (DeviceBuffer* b : bufs) b->release();
     if (f->pin_in) (void)hipHostFree(f->pin_in);
@@ -156,7 +213,7 @@ int frame_init_check(icp_ctx* ctx, const icp_frame_config* cfg, bool own_batch) 
     if (rc) return rc;
     if ((cfg->targets != 0 && cfg->targets != 1) || !(cfg->threshold_trans >= 0.f) || !(cfg->threshold_rot >= 0.f))
         return frame_fail(ctx, "icp_odometry_init: targets is 0 or 1, the key-frame thresholds are not negative");
-    if (!own_batch && ctx->frame && ctx->frame->launched && ctx->frame->batched)
+    if (!own_batch && ctx->frame && ctx->frame->seq.launched && ctx->frame->seq.batched)
         return frame_fail(ctx, "icp_odometry_init: a frame launched by a batch awaits icp_batch_frame_end");
     return ICP_OK;
 }
@@ -164,7 +221,7 @@ int frame_init_check(icp_ctx* ctx, const icp_frame_config* cfg, bool own_batch) 
 void frame_loop_release(icp_ctx* ctx) {
     icp_frame_loop* f = ctx ? ctx->frame : nullptr;
     if (!f) return;
-    frame_buffers_release(f);
+    frame_buffers_release(&f->io);
     delete f;
     ctx->frame = nullptr;
 }
@@ -192,13 +249,13 @@ int icp_odometry_init(icp_ctx* ctx, const icp_frame_config* cfg) {
     if (rc) return rc;
     if (!ctx->frame) ctx->frame = new icp_frame_loop();
     icp_frame_loop* f = ctx->frame;
-    frame_drop_pending(ctx, f);
+    frame_drop_pending(ctx, &f->seq, &f->io);
     if ((rc = icp_map_init(ctx))) return rc;
     f->cfg = *cfg;
-    f->index = 0;
+    f->seq.index = 0;
     f->pose_epoch = -1;
-    pose_identity(f->delta);
-    pose_identity(f->last_pose);
+    pose_identity(f->seq.delta);
+    pose_identity(f->seq.last_pose);
     return ICP_OK;
 }
 
@@ -210,7 +267,7 @@ int icp_frame_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, const d
     if (!f) return frame_fail(ctx, "icp_frame_launch: no sequence (icp_odometry_init first)");
     int rc = frame_refusals(ctx, "icp_frame_launch");
     if (rc) return rc;
-    if (f->launched) return frame_fail(ctx, "icp_frame_launch: a frame is already launched (icp_frame_end first)");
+    if (f->seq.launched) return frame_fail(ctx, "icp_frame_launch: a frame is already launched (icp_frame_end first)");
     if (n < 0 || n > INT32_MAX || (n > 0 && !xyz) || (mem != ICP_MEM_HOST && mem != ICP_MEM_DEVICE))
         return frame_fail(ctx, "icp_frame_launch: [n,3] rows in host or device memory are required");
     if (ctx->in_registration || ctx->result_pending())
@@ -218,7 +275,7 @@ int icp_frame_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, const d
     // ---- input
     const float* rows = xyz;
     const double* ts = timestamps;
-    if (n > 0 && mem == ICP_MEM_HOST && (rc = frame_upload(ctx, f, xyz, timestamps, n, &rows, &ts))) return rc;
+    if (n > 0 && mem == ICP_MEM_HOST && (rc = frame_upload(ctx, &f->io, xyz, timestamps, n, &rows, &ts))) return rc;
     return frame_launch_device(ctx, rows, n, ts, init_pose);
 }
 
@@ -230,39 +287,41 @@ namespace icp {
 // of a member through here, behind the batch's own upload)
 int frame_launch_device(icp_ctx* ctx, const float* rows, int64_t n, const double* ts, const float init_pose[16]) {
     icp_frame_loop* f = ctx->frame;
+    icp_frame_seq& s = f->seq;
+    icp_frame_io& io = f->io;
     int rc;
     const icp_frame_config& c = f->cfg;
     // ---- the initial guess (ConstantVelocityInitialization, slam/initialization.py:103-119)
     const bool have_guess = init_pose != nullptr || c.constant_velocity != 0;
-    const float* guess = init_pose ? init_pose : f->last_pose;  // (identity without constant_velocity: see below)
+    const float* guess = init_pose ? init_pose : s.last_pose;  // (identity without constant_velocity: see below)
     // ---- de-skew -> grid sample -> float32 (slam/preprocessing.py:144-191, :207-226, :101-126)
     bool sample = false;
-    if ((rc = frame_preprocess_device(ctx, f, c.voxel_size, rows, n, ts, have_guess ? guess : nullptr, &rows, &sample))) return rc;
+    if ((rc = frame_preprocess_device(ctx, &io, c.voxel_size, rows, n, ts, have_guess ? guess : nullptr, &rows, &sample))) return rc;
     f->frame_rows = rows;
-    f->n = n;
-    f->sampled = sample;
-    f->copy_started = false;
+    s.n = n;
+    s.sampled = sample;
+    io.copy_started = false;
     const size_t npix = (size_t)ctx->cfg.height * ctx->cfg.width;
     // ---- frame 0: the vertex map goes into the map (:176)
-    if (f->index == 0) {
-        ICP_HIP(ctx, f->vmap.reserve(npix * 12));
+    if (s.index == 0) {
+        ICP_HIP(ctx, io.vmap.reserve(npix * 12));
         if (c.targets == 1) {
-            ICP_HIP(ctx, f->rows.reserve(npix * 12));
-            rc = icp_project_rows(ctx, rows, n, f->vmap.as<float>(), f->rows.as<float>());
+            ICP_HIP(ctx, io.rows.reserve(npix * 12));
+            rc = icp_project_rows(ctx, rows, n, io.vmap.as<float>(), io.rows.as<float>());
         } else {
-            rc = icp_project(ctx, rows, n, ICP_MEM_DEVICE, f->vmap.as<float>(), nullptr, ICP_MEM_DEVICE);
+            rc = icp_project(ctx, rows, n, ICP_MEM_DEVICE, io.vmap.as<float>(), nullptr, ICP_MEM_DEVICE);
         }
         if (rc) return rc;
         if (sample) {  // (the insertion below waits for its own count: this one arrives with it)
-            if (!f->pin_count) ICP_HIP(ctx, hipHostMalloc((void**)&f->pin_count, sizeof(int), hipHostMallocDefault));
-            ICP_HIP(ctx, hipMemcpyAsync(f->pin_count, f->count.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            if (!io.pin_count) ICP_HIP(ctx, hipHostMalloc((void**)&io.pin_count, sizeof(int), hipHostMallocDefault));
+            ICP_HIP(ctx, hipMemcpyAsync(io.pin_count, io.count.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         }
         float eye[16];
         pose_identity(eye);
         f->inserted0 = 0;
-        if ((rc = icp_map_update_vertex_map(ctx, eye, f->vmap.as<float>(), ICP_MEM_DEVICE, &f->inserted0))) return rc;
-        f->launched = true;
-        f->registered = false;
+        if ((rc = icp_map_update_vertex_map(ctx, eye, io.vmap.as<float>(), ICP_MEM_DEVICE, &f->inserted0))) return rc;
+        s.launched = true;
+        s.registered = false;
         return ICP_OK;
     }
     // ---- later frames: projection (targets = 1), staging, copy-out, registration — the plugin's order
@@ -270,21 +329,21 @@ int frame_launch_device(icp_ctx* ctx, const float* rows, int64_t n, const double
     int64_t n_targets = n;
     int target_mode = ICP_TARGETS_ALL;
     if (c.targets == 1) {
-        ICP_HIP(ctx, f->vmap.reserve(npix * 12));
-        ICP_HIP(ctx, f->rows.reserve(npix * 12));
-        if ((rc = icp_project_rows(ctx, rows, n, f->vmap.as<float>(), f->rows.as<float>()))) return rc;
-        targets = f->rows.as<float>();
+        ICP_HIP(ctx, io.vmap.reserve(npix * 12));
+        ICP_HIP(ctx, io.rows.reserve(npix * 12));
+        if ((rc = icp_project_rows(ctx, rows, n, io.vmap.as<float>(), io.rows.as<float>()))) return rc;
+        targets = io.rows.as<float>();
         n_targets = (int64_t)npix;
         target_mode = ICP_TARGETS_SKIP_NULL;
     }
     // (a frame that comes padded from the grid sample — a handful of valid rows among NaN rows — is staged whatever its row
     // count; a large raw frame only when its copy-out needs the compacted rows anyway)
-    f->staged = sample || c.stage_max_rows <= 0 || n <= (int64_t)c.stage_max_rows || c.copy_cloud != 0;
-    if (f->staged && (rc = icp_map_stage_cloud(ctx, rows, n, ICP_MEM_DEVICE, ICP_TARGETS_ALL))) return rc;
-    if (f->staged && (sample || (c.copy_cloud && n > 0))) {
-        if ((rc = frame_copy_start(ctx, f, sample, c.copy_cloud && n > 0, n))) return rc;
+    s.staged = sample || c.stage_max_rows <= 0 || n <= (int64_t)c.stage_max_rows || c.copy_cloud != 0;
+    if (s.staged && (rc = icp_map_stage_cloud(ctx, rows, n, ICP_MEM_DEVICE, ICP_TARGETS_ALL))) return rc;
+    if (s.staged && (sample || (c.copy_cloud && n > 0))) {
+        if ((rc = frame_copy_start(ctx, &io, sample, c.copy_cloud && n > 0, n))) return rc;
     }
-    const bool from_last = c.constant_velocity != 0 && !init_pose && f->index >= 2 && ctx->have_device_pose &&
+    const bool from_last = c.constant_velocity != 0 && !init_pose && s.index >= 2 && ctx->have_device_pose &&
                            f->pose_epoch == ctx->device_pose_epoch;
     if (from_last) {
         rc = icp_register_launch_from_last(ctx, targets, n_targets, ICP_MEM_DEVICE, target_mode);
@@ -294,13 +353,13 @@ int frame_launch_device(icp_ctx* ctx, const float* rows, int64_t n, const double
         rc = icp_register_launch(ctx, targets, n_targets, ICP_MEM_DEVICE, target_mode, have_guess ? guess : eye);
     }
     if (rc) {
-        if (f->copy_started) (void)hipEventSynchronize(f->copy_done);
-        f->copy_started = false;
+        if (io.copy_started) (void)hipEventSynchronize(io.copy_done);
+        io.copy_started = false;
         return rc;
     }
     f->pose_epoch = ctx->device_pose_epoch;
-    f->launched = true;
-    f->registered = true;
+    s.launched = true;
+    s.registered = true;
     return ICP_OK;
 }
 
@@ -313,72 +372,35 @@ int icp_frame_end(icp_ctx* ctx, icp_frame_result* result, float* odometry_pc_out
     if (!ctx || !result) return ICP_ERR_INVALID_ARGUMENT;
     DeviceGuard device_guard(ctx, false);  // (the entry points composed below join the map stream where they must)
     icp_frame_loop* f = ctx->frame;
-    if (!f || !f->launched) return frame_fail(ctx, "icp_frame_end: no frame launched (icp_frame_launch first)");
+    if (!f || !f->seq.launched) return frame_fail(ctx, "icp_frame_end: no frame launched (icp_frame_launch first)");
     if (ctx->batch_hold) return frame_fail(ctx, "icp_frame_end: the context is held by a batched registration");
-    if (f->batched) return frame_fail(ctx, "icp_frame_end: the frame was launched by a batch (icp_batch_frame_end ends it)");
+    if (f->seq.batched) return frame_fail(ctx, "icp_frame_end: the frame was launched by a batch (icp_batch_frame_end ends it)");
     if (odometry_pc_out && cap < 0) return frame_fail(ctx, "icp_frame_end: negative capacity");
+    icp_frame_seq& s = f->seq;
     memset(result, 0, sizeof(*result));
-    result->frame_index = f->index;
+    result->frame_index = s.index;
     if (rows_out) *rows_out = 0;
-    int rc;
-    if (!f->registered) {  // frame 0: the identity, the vertex map is in the map (the insertion waited for its count)
-        pose_identity(result->reg.pose);
-        result->key_frame = 1;
-        result->inserted = f->inserted0;
-        result->samples = f->sampled ? (int64_t)*f->pin_count : f->n;
-        f->launched = false;
-        f->index += 1;
-        return ICP_OK;
-    }
-    rc = icp_register_end(ctx, &result->reg, loss_per_iter_out, dx_per_iter_out);
-    if (f->copy_started) {
-        ICP_HIP(ctx, hipEventSynchronize(f->copy_done));
-    }
-    result->samples = f->sampled && f->copy_started ? (int64_t)*f->pin_count : f->n;
-    if (rc) {  // the reference raises before it touches the map (:286): nothing of the sequence moves
-        f->launched = f->registered = false;
-        f->copy_started = false;
-        f->pose_epoch = -1;
+    // frame 0: the identity, the vertex map is in the map (the insertion waited for its count)
+    if (!s.registered) return frame_end_first(ctx, &s, &f->io, f->inserted0, false, result);
+    int rc = frame_collect(ctx, &s, &f->io, result, loss_per_iter_out, dx_per_iter_out);
+    if (rc) {
+        if (!s.launched) f->pose_epoch = -1;  // (a failed registration; a failed wait leaves the frame launched)
         return rc;
     }
     // ---- __update_map (:360-380)
-    const KeyFrameTest t = key_frame_test(f->delta, result->reg.pose, f->cfg.threshold_trans, f->cfg.threshold_rot);
+    const KeyFrameTest t = key_frame_test(s.delta, result->reg.pose, f->cfg.threshold_trans, f->cfg.threshold_rot);
     result->key_frame = t.key_frame;
-    f->launched = f->registered = false;
-    if (t.key_frame) {
-        rc = f->staged ? icp_map_update_staged(ctx, result->reg.pose, &result->inserted)
-                       : icp_map_update(ctx, result->reg.pose, f->frame_rows, f->n, ICP_MEM_DEVICE, ICP_TARGETS_ALL,
-                                        &result->inserted);  // (n > stage_max_rows > 0: never an empty cloud)
-        if (!rc) pose_identity(f->delta);
-    } else {
-        rc = icp_map_update(ctx, result->reg.pose, nullptr, 0, ICP_MEM_DEVICE, ICP_TARGETS_ALL, nullptr);
-        if (!rc) memcpy(f->delta, t.new_delta, sizeof(f->delta));
-    }
-    const bool copied = f->copy_started && f->cfg.copy_cloud && f->n > 0;
-    f->copy_started = false;
+    s.launched = s.registered = false;
+    if (!t.key_frame) rc = icp_map_update(ctx, result->reg.pose, nullptr, 0, ICP_MEM_DEVICE, ICP_TARGETS_ALL, nullptr);
+    else if (s.staged) rc = icp_map_update_staged(ctx, result->reg.pose, &result->inserted);
+    else  // (n > stage_max_rows > 0: never an empty cloud)
+        rc = icp_map_update(ctx, result->reg.pose, f->frame_rows, s.n, ICP_MEM_DEVICE, ICP_TARGETS_ALL, &result->inserted);
+    const bool copied = f->io.copy_started && f->cfg.copy_cloud && s.n > 0;
+    f->io.copy_started = false;
     if (rc) return rc;
-    memcpy(f->last_pose, result->reg.pose, sizeof(f->last_pose));
-    f->index += 1;
-    // ---- odometry_pc (:210-213, :243): the valid rows the staging compacted, in order
-    if (!f->staged && odometry_pc_out) {  // (not staged in front of the registration: compacted now)
-        if ((rc = icp_map_stage_cloud(ctx, f->frame_rows, f->n, ICP_MEM_DEVICE, ICP_TARGETS_ALL))) return rc;
-        ICP_HIP(ctx, hipEventSynchronize(ctx->staged_event));
-    }
-    const int64_t valid = f->n > 0 && (f->staged || odometry_pc_out) ? (int64_t)*ctx->staged_count_host : 0;
-    if (rows_out) *rows_out = valid;
-    if (odometry_pc_out) {
-        if (valid > cap) return frame_fail(ctx, "icp_frame_end: odometry_pc_out holds fewer rows than the frame has (count in *rows_out)");
-        if (valid > 0 && out_mem == ICP_MEM_HOST && copied) {
-            memcpy(odometry_pc_out, f->pin_out, (size_t)valid * 12);
-        } else if (valid > 0) {
-            // (not copied ahead, or a device buffer: behind the map update just enqueued, which reads the staged rows and
-            // leaves them as they are)
-            ICP_HIP(ctx, hipMemcpyAsync(odometry_pc_out, ctx->staged_xyz.ptr, (size_t)valid * 12,
-                                        out_mem == ICP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-            if (out_mem == ICP_MEM_HOST) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
-    return ICP_OK;
+    frame_advance(&s, t, result->reg.pose);
+    return frame_deliver(ctx, "icp_frame_end", &s, &f->io, copied, !s.staged && odometry_pc_out, f->frame_rows, ICP_TARGETS_ALL,
+                         odometry_pc_out, cap, rows_out, out_mem);
 }
 
 }  // extern "C"

@@ -1,11 +1,11 @@
 // One call per odometry frame against the projective local map: icp_pmap_odometry_init / icp_pmap_frame_launch /
 // icp_pmap_frame_end (include/icp_mi355x.h).  ICPFrameToModel.do_process_next_frame (slam/odometry/icp_odometry.py:157-246) with
 // ProjectiveLocalMap (slam/odometry/local_map.py:113-235), composed from the entry points of api.hip in the order
-// pylidar_slam_amd/odometry.py::MI355XICPFrameToModel issues them; host code only — every launch is one of theirs.  The upload,
-// the preprocessing chain and the copy-out are those of frame.hip (frame_loop.h).
+// pylidar_slam_amd/odometry.py::MI355XICPFrameToModel issues them; host code only — every launch is one of theirs.  What is
+// particular to the projective map lives here — the refusals, the input section of the launch, the update call; every other
+// step of a frame is frame.hip's (frame_loop.h).
 #include <string.h>
 
-#include "frame_keyframe.h"
 #include "frame_loop.h"
 #include "icp_internal.h"
 
@@ -25,18 +25,6 @@ int pframe_refusals(icp_ctx* ctx, const char* who) {
     if (ctx->frame)
         return pframe_fail(ctx, std::string(who) + ": a kd-tree sequence (icp_odometry_init) runs on this context");
     return ICP_OK;
-}
-
-// a frame launched and never ended: its registration is collected and dropped, its copy waited for
-void pframe_drop_pending(icp_ctx* ctx, icp_pmap_frame_loop* f) {
-    if (!f->launched) return;
-    if (f->registered && ctx->result_pending()) {
-        icp_register_result r;
-        (void)icp_register_end(ctx, &r, nullptr, nullptr);
-    }
-    if (f->io.copy_started) (void)hipEventSynchronize(f->io.copy_done);
-    f->io.copy_started = false;
-    f->launched = f->registered = false;
 }
 
 }  // namespace
@@ -60,9 +48,9 @@ int pmap_frame_init_check(icp_ctx* ctx, const icp_pmap_frame_config* cfg, bool o
     if (cfg->normals_kernel_size < 1 || cfg->normals_kernel_size > 15 || !(cfg->normals_kernel_size & 1))
         return pframe_fail(ctx, "icp_pmap_odometry_init: normals_kernel_size must be odd, 1..15");
     const icp_pmap_frame_loop* f = ctx->pframe;
-    if (!own_batch && f && f->launched && f->batched)
+    if (!own_batch && f && f->seq.launched && f->seq.batched)
         return pframe_fail(ctx, "icp_pmap_odometry_init: a frame launched by a batch awaits icp_batch_pmap_frame_end");
-    if ((ctx->in_registration || ctx->result_pending()) && !(f && f->launched && f->registered))
+    if ((ctx->in_registration || ctx->result_pending()) && !(f && f->seq.launched && f->seq.registered))
         return pframe_fail(ctx, "icp_pmap_odometry_init: a registration of this context is in progress or awaits icp_register_end");
     return ICP_OK;
 }
@@ -90,12 +78,12 @@ int icp_pmap_odometry_init(icp_ctx* ctx, const icp_pmap_frame_config* cfg) {
     if (rc) return rc;
     icp_pmap_frame_loop* f = ctx->pframe;
     if (!f) f = ctx->pframe = new icp_pmap_frame_loop();
-    pframe_drop_pending(ctx, f);
+    frame_drop_pending(ctx, &f->seq, &f->io);
     if ((rc = icp_pmap_init(ctx))) return rc;
     f->cfg = *cfg;
-    f->index = 0;
-    pose_identity(f->delta);
-    pose_identity(f->last_pose);
+    f->seq.index = 0;
+    pose_identity(f->seq.delta);
+    pose_identity(f->seq.last_pose);
     return ICP_OK;
 }
 
@@ -107,7 +95,7 @@ int icp_pmap_frame_launch(icp_ctx* ctx, const float* data, int64_t n, int mem, i
     if (!f) return pframe_fail(ctx, "icp_pmap_frame_launch: no sequence (icp_pmap_odometry_init first)");
     int rc = pframe_refusals(ctx, "icp_pmap_frame_launch");
     if (rc) return rc;
-    if (f->launched) return pframe_fail(ctx, "icp_pmap_frame_launch: a frame is already launched (icp_pmap_frame_end first)");
+    if (f->seq.launched) return pframe_fail(ctx, "icp_pmap_frame_launch: a frame is already launched (icp_pmap_frame_end first)");
     const icp_pmap_frame_config& c = f->cfg;
     const int64_t npix = (int64_t)ctx->cfg.height * ctx->cfg.width;
     if (layout != ICP_FRAME_ROWS && layout != ICP_FRAME_VERTEX_MAP)
@@ -125,13 +113,13 @@ int icp_pmap_frame_launch(icp_ctx* ctx, const float* data, int64_t n, int mem, i
         return pframe_fail(ctx, "icp_pmap_frame_launch: a registration of this context is in progress or awaits icp_register_end");
     // ---- the initial guess (ConstantVelocityInitialization, slam/initialization.py:103-119)
     const bool have_guess = init_pose != nullptr || c.constant_velocity != 0;
-    const float* guess = init_pose ? init_pose : f->last_pose;
+    const float* guess = init_pose ? init_pose : f->seq.last_pose;
     float eye[16];
     pose_identity(eye);
-    f->n = n;
-    f->sampled = false;
+    f->seq.n = n;
+    f->seq.sampled = false;
     f->io.copy_started = false;
-    f->staged = false;
+    f->seq.staged = false;
     // ---- input: the targets, the rows odometry_pc is made of, the vertex map a key frame inserts
     const float* targets = nullptr;
     int64_t n_targets = 0;
@@ -140,7 +128,7 @@ int icp_pmap_frame_launch(icp_ctx* ctx, const float* data, int64_t n, int mem, i
     bool project_behind = false;
     if (from_vmap) {
         f->frame_vmap = data;
-        if (f->index > 0) {  // the pixels as rows (sample_points :301-308)
+        if (f->seq.index > 0) {  // the pixels as rows (sample_points :301-308)
             ICP_HIP(ctx, f->io.rows.reserve((size_t)npix * 12));
             if ((rc = vmap_rows_device(ctx, data, f->io.rows.as<float>()))) return rc;
         }
@@ -150,13 +138,13 @@ int icp_pmap_frame_launch(icp_ctx* ctx, const float* data, int64_t n, int mem, i
     } else {
         const double* ts = timestamps;
         if (n > 0 && mem == ICP_MEM_HOST && (rc = frame_upload(ctx, &f->io, data, timestamps, n, &rows, &ts))) return rc;
-        if ((rc = frame_preprocess_device(ctx, &f->io, c.voxel_size, rows, n, ts, have_guess ? guess : nullptr, &rows, &f->sampled)))
+        if ((rc = frame_preprocess_device(ctx, &f->io, c.voxel_size, rows, n, ts, have_guess ? guess : nullptr, &rows, &f->seq.sampled)))
             return rc;
         ICP_HIP(ctx, f->io.vmap.reserve((size_t)npix * 12));
         f->frame_vmap = f->io.vmap.as<float>();
         f->valid_rows = rows;
         f->valid_mode = ICP_TARGETS_ALL;
-        if (f->index == 0) {
+        if (f->seq.index == 0) {
             if ((rc = icp_project(ctx, rows, n, ICP_MEM_DEVICE, f->io.vmap.as<float>(), nullptr, ICP_MEM_DEVICE))) return rc;
         } else if (c.targets == 1) {
             ICP_HIP(ctx, f->io.rows.reserve((size_t)npix * 12));
@@ -171,28 +159,28 @@ int icp_pmap_frame_launch(icp_ctx* ctx, const float* data, int64_t n, int mem, i
         }
     }
     // ---- frame 0: the vertex map goes into the map (:176)
-    if (f->index == 0) {
-        if (f->sampled) {  // (collected in icp_pmap_frame_end)
+    if (f->seq.index == 0) {
+        if (f->seq.sampled) {  // (collected in icp_pmap_frame_end)
             if (!f->io.pin_count) ICP_HIP(ctx, hipHostMalloc((void**)&f->io.pin_count, sizeof(int), hipHostMallocDefault));
             ICP_HIP(ctx, hipMemcpyAsync(f->io.pin_count, f->io.count.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         }
         if ((rc = icp_pmap_update(ctx, eye, f->frame_vmap, ICP_MEM_DEVICE, c.normals_kernel_size))) return rc;
-        f->launched = true;
-        f->registered = false;
+        f->seq.launched = true;
+        f->seq.registered = false;
         return ICP_OK;
     }
     // ---- later frames: the valid rows compacted and on their way to the host, then the registration
-    f->staged = n > 0 && (f->sampled || c.copy_cloud != 0);
-    if (f->staged && (rc = icp_map_stage_cloud(ctx, f->valid_rows, n, ICP_MEM_DEVICE, f->valid_mode))) return rc;
-    if (f->staged && (rc = frame_copy_start(ctx, &f->io, f->sampled, c.copy_cloud != 0, n))) return rc;
+    f->seq.staged = n > 0 && (f->seq.sampled || c.copy_cloud != 0);
+    if (f->seq.staged && (rc = icp_map_stage_cloud(ctx, f->valid_rows, n, ICP_MEM_DEVICE, f->valid_mode))) return rc;
+    if (f->seq.staged && (rc = frame_copy_start(ctx, &f->io, f->seq.sampled, c.copy_cloud != 0, n))) return rc;
     rc = icp_pmap_register_launch(ctx, targets, n_targets, ICP_MEM_DEVICE, target_mode, have_guess ? guess : eye);
     if (rc) {
         if (f->io.copy_started) (void)hipEventSynchronize(f->io.copy_done);
         f->io.copy_started = false;
         return rc;
     }
-    f->launched = true;
-    f->registered = true;
+    f->seq.launched = true;
+    f->seq.registered = true;
     if (project_behind && (rc = icp_project(ctx, rows, n, ICP_MEM_DEVICE, f->io.vmap.as<float>(), nullptr, ICP_MEM_DEVICE)))
         return rc;  // (the frame stays launched: icp_pmap_frame_end collects its registration)
     return ICP_OK;
@@ -203,68 +191,30 @@ int icp_pmap_frame_end(icp_ctx* ctx, icp_frame_result* result, float* odometry_p
     if (!ctx || !result) return ICP_ERR_INVALID_ARGUMENT;
     DeviceGuard device_guard(ctx, false);
     icp_pmap_frame_loop* f = ctx->pframe;
-    if (!f || !f->launched) return pframe_fail(ctx, "icp_pmap_frame_end: no frame launched (icp_pmap_frame_launch first)");
+    if (!f || !f->seq.launched) return pframe_fail(ctx, "icp_pmap_frame_end: no frame launched (icp_pmap_frame_launch first)");
     if (ctx->batch_hold) return pframe_fail(ctx, "icp_pmap_frame_end: the context is held by a batched registration");
-    if (f->batched) return pframe_fail(ctx, "icp_pmap_frame_end: the frame was launched by a batch (icp_batch_pmap_frame_end ends it)");
+    if (f->seq.batched) return pframe_fail(ctx, "icp_pmap_frame_end: the frame was launched by a batch (icp_batch_pmap_frame_end ends it)");
     if (odometry_pc_out && cap < 0) return pframe_fail(ctx, "icp_pmap_frame_end: negative capacity");
+    icp_frame_seq& s = f->seq;
     memset(result, 0, sizeof(*result));
-    result->frame_index = f->index;
+    result->frame_index = s.index;
     if (rows_out) *rows_out = 0;
-    int rc;
-    if (!f->registered) {  // frame 0: the identity, the vertex map is in the map
-        if (f->sampled) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the grid sample's count)
-        pose_identity(result->reg.pose);
-        result->key_frame = 1;
-        result->inserted = 1;
-        result->samples = f->sampled ? (int64_t)*f->io.pin_count : f->n;
-        f->launched = false;
-        f->index += 1;
-        return ICP_OK;
-    }
-    rc = icp_register_end(ctx, &result->reg, loss_per_iter_out, dx_per_iter_out);
-    if (f->io.copy_started) ICP_HIP(ctx, hipEventSynchronize(f->io.copy_done));
-    result->samples = f->sampled && f->io.copy_started ? (int64_t)*f->io.pin_count : f->n;
-    if (rc) {  // the reference raises before it touches the map (:286): nothing of the sequence moves
-        f->launched = f->registered = false;
-        f->io.copy_started = false;
-        return rc;
-    }
+    // frame 0: the identity, the vertex map is in the map (nothing has waited for the grid sample's count yet)
+    if (!s.registered) return frame_end_first(ctx, &s, &f->io, 1, true, result);
+    int rc = frame_collect(ctx, &s, &f->io, result, loss_per_iter_out, dx_per_iter_out);
+    if (rc) return rc;
     // ---- __update_map (:360-380) with ProjectiveLocalMap.update (local_map.py:122-174)
-    const KeyFrameTest t = key_frame_test(f->delta, result->reg.pose, f->cfg.threshold_trans, f->cfg.threshold_rot);
+    const KeyFrameTest t = key_frame_test(s.delta, result->reg.pose, f->cfg.threshold_trans, f->cfg.threshold_rot);
     result->key_frame = t.key_frame;
-    f->launched = f->registered = false;
-    if (t.key_frame) {
-        rc = icp_pmap_update(ctx, result->reg.pose, f->frame_vmap, ICP_MEM_DEVICE, f->cfg.normals_kernel_size);
-        if (!rc) pose_identity(f->delta);
-        if (!rc) result->inserted = 1;
-    } else {
-        rc = icp_pmap_update(ctx, result->reg.pose, nullptr, ICP_MEM_DEVICE, f->cfg.normals_kernel_size);
-        if (!rc) memcpy(f->delta, t.new_delta, sizeof(f->delta));
-    }
-    const bool copied = f->io.copy_started && f->cfg.copy_cloud && f->n > 0;
+    s.launched = s.registered = false;
+    rc = icp_pmap_update(ctx, result->reg.pose, t.key_frame ? f->frame_vmap : nullptr, ICP_MEM_DEVICE, f->cfg.normals_kernel_size);
+    if (!rc && t.key_frame) result->inserted = 1;
+    const bool copied = f->io.copy_started && f->cfg.copy_cloud && s.n > 0;
     f->io.copy_started = false;
     if (rc) return rc;
-    memcpy(f->last_pose, result->reg.pose, sizeof(f->last_pose));
-    f->index += 1;
-    // ---- odometry_pc (:210-213, :243): the valid rows the staging compacted, in order
-    if (!f->staged && odometry_pc_out && f->n > 0) {  // (not staged in front of the registration: compacted now)
-        if ((rc = icp_map_stage_cloud(ctx, f->valid_rows, f->n, ICP_MEM_DEVICE, f->valid_mode))) return rc;
-        ICP_HIP(ctx, hipEventSynchronize(ctx->staged_event));
-    }
-    const int64_t valid = f->n > 0 && (f->staged || odometry_pc_out) ? (int64_t)*ctx->staged_count_host : 0;
-    if (rows_out) *rows_out = valid;
-    if (odometry_pc_out) {
-        if (valid > cap)
-            return pframe_fail(ctx, "icp_pmap_frame_end: odometry_pc_out holds fewer rows than the frame has (count in *rows_out)");
-        if (valid > 0 && out_mem == ICP_MEM_HOST && copied) {
-            memcpy(odometry_pc_out, f->io.pin_out, (size_t)valid * 12);
-        } else if (valid > 0) {
-            ICP_HIP(ctx, hipMemcpyAsync(odometry_pc_out, ctx->staged_xyz.ptr, (size_t)valid * 12,
-                                        out_mem == ICP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-            if (out_mem == ICP_MEM_HOST) ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
-    return ICP_OK;
+    frame_advance(&s, t, result->reg.pose);
+    return frame_deliver(ctx, "icp_pmap_frame_end", &s, &f->io, copied, !s.staged && odometry_pc_out && s.n > 0, f->valid_rows,
+                         f->valid_mode, odometry_pc_out, cap, rows_out, out_mem);
 }
 
 }  // extern "C"

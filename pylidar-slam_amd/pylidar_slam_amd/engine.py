@@ -86,17 +86,60 @@ def _on_device(*arrays) -> bool:
 _FRAME_CONFIG_FIELDS = {"voxel_size": float, "threshold_trans": float, "threshold_rot": float,
                         "constant_velocity": lambda v: int(bool(v)), "targets": int, "copy_cloud": lambda v: int(bool(v)),
                         "stage_max_rows": int}
+_PMAP_FRAME_CONFIG_FIELDS = {k: v for k, v in _FRAME_CONFIG_FIELDS.items() if k != "stage_max_rows"}
+_PMAP_FRAME_CONFIG_FIELDS["normals_kernel_size"] = int
+
+
+def _fill_config(cfg, fields, who: str, kw):
+    for k, v in kw.items():
+        if k not in fields:
+            raise TypeError(f"{who}() got an unexpected keyword argument {k!r}")
+        setattr(cfg, k, fields[k](v))
+    return cfg
 
 
 def _frame_config(lib, **kw) -> IcpFrameConfig:
     """icp_default_frame_config with the given fields set (`IcpContext.odometry_init` and `IcpBatch.odometry_init`)."""
     cfg = IcpFrameConfig()
     lib.icp_default_frame_config(C.byref(cfg))
-    for k, v in kw.items():
-        if k not in _FRAME_CONFIG_FIELDS:
-            raise TypeError(f"odometry_init() got an unexpected keyword argument {k!r}")
-        setattr(cfg, k, _FRAME_CONFIG_FIELDS[k](v))
-    return cfg
+    return _fill_config(cfg, _FRAME_CONFIG_FIELDS, "odometry_init", kw)
+
+
+def _pmap_frame_config(lib, **kw) -> IcpPmapFrameConfig:
+    """icp_default_pmap_frame_config with the given fields set (the two `pmap_odometry_init`s)."""
+    cfg = IcpPmapFrameConfig()
+    lib.icp_default_pmap_frame_config(C.byref(cfg))
+    return _fill_config(cfg, _PMAP_FRAME_CONFIG_FIELDS, "pmap_odometry_init", kw)
+
+
+def _frame_arrays(data, timestamps=None, vertex_map: bool = False, who: str = "", rows_alt: str = ""):
+    """One frame as the frame calls take it: [N,3] float32 rows on the host (numpy, cpu tensor) or on the device (cuda
+    tensor) with optional [N] float64 timestamps where the rows live, or — `vertex_map` — a cuda [3,H,W] / [1,3,H,W]
+    vertex map.  Returns (pointer, n, mem, layout, timestamp pointer, keep); `keep` holds what the pointers point into.
+    `who` / `rows_alt`: the caller's words in the messages."""
+    if vertex_map:
+        vm = data[0] if data.ndim == 4 else data
+        if (data.ndim == 4 and data.shape[0] != 1) or vm.shape[0] != 3:
+            raise AssertionError(f"{who}expected a [3,H,W] vertex map, got {tuple(data.shape)}")
+        vm = vm if vm.dtype == torch.float32 and vm.is_contiguous() else vm.to(torch.float32).contiguous()
+        ts = None if timestamps is None else torch.as_tensor(timestamps).to(vm.device, torch.float64)
+        return vm.data_ptr(), int(vm.shape[1] * vm.shape[2]), MEM_DEVICE, FRAME_VERTEX_MAP, \
+            (ts.data_ptr() if ts is not None else None), (vm, ts)
+    if isinstance(data, torch.Tensor) and data.is_cuda:
+        pts = data if data.dtype == torch.float32 and data.is_contiguous() else data.to(torch.float32).contiguous()
+        ts = None if timestamps is None else \
+            torch.as_tensor(timestamps).to(pts.device, torch.float64).reshape(-1).contiguous()
+        mem, p, tp = MEM_DEVICE, pts.data_ptr(), ts.data_ptr() if ts is not None else None
+    else:
+        pts = data.numpy() if isinstance(data, torch.Tensor) else data
+        if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.flags.c_contiguous):
+            pts = np.ascontiguousarray(pts, dtype=np.float32)
+        ts = None if timestamps is None else np.ascontiguousarray(np.asarray(timestamps).reshape(-1), dtype=np.float64)
+        mem, p, tp = MEM_HOST, pts.ctypes.data, ts.ctypes.data if ts is not None else None
+    if pts.ndim != 2 or pts.shape[1] != 3 or (ts is not None and ts.shape[0] != pts.shape[0]):
+        raise AssertionError(f"{who}expected [N,3] points (and [N] timestamps){rows_alt}, got {tuple(pts.shape)}")
+    n = int(pts.shape[0])
+    return (p if n else None), n, mem, FRAME_ROWS, (tp if n else None), (pts, ts)
 
 
 def _pose16(m) -> "C.Array":
@@ -874,35 +917,24 @@ class IcpContext:
         cuda tensor (used in place: keep it untouched until `frame_end`) — enqueued without waiting.  timestamps [N]
         float64 (where the points live): the frame is de-skewed by its initial guess.  init_pose: an explicit guess."""
         self._bind(points)
-        if isinstance(points, torch.Tensor) and points.is_cuda:
-            pts = points if points.dtype == torch.float32 and points.is_contiguous() else \
-                points.to(torch.float32).contiguous()
-            ts = None
-            if timestamps is not None:
-                ts = torch.as_tensor(timestamps).to(pts.device, torch.float64).reshape(-1).contiguous()
-            mem, p, tp = MEM_DEVICE, pts.data_ptr(), ts.data_ptr() if ts is not None else None
-        else:
-            pts = points.numpy() if isinstance(points, torch.Tensor) else points
-            if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.flags.c_contiguous):
-                pts = np.ascontiguousarray(pts, dtype=np.float32)
-            ts = None
-            if timestamps is not None:
-                ts = np.ascontiguousarray(np.asarray(timestamps).reshape(-1), dtype=np.float64)
-            mem, p, tp = MEM_HOST, pts.ctypes.data, ts.ctypes.data if ts is not None else None
-        if pts.ndim != 2 or pts.shape[1] != 3 or (ts is not None and ts.shape[0] != pts.shape[0]):
-            raise AssertionError(f"expected [N,3] points (and [N] timestamps), got {tuple(pts.shape)}")
-        n = int(pts.shape[0])
-        self._check(self._lib.icp_frame_launch(self._h, p if n else None, n, mem, tp if n else None,
-                                               _pose16(init_pose) if init_pose is not None else None))
-        self._frame_keep = (pts, ts) if mem == MEM_DEVICE else None
+        p, n, mem, _, tp, keep = _frame_arrays(points, timestamps)
+        self._check(self._lib.icp_frame_launch(self._h, p, n, mem, tp, _pose16(init_pose) if init_pose is not None else None))
+        self._frame_launched(keep, n, mem)
+
+    def _frame_launched(self, keep, n: int, mem: int):
+        self._frame_keep = keep if mem == MEM_DEVICE else None  # (device data stays alive until the frame's end)
         self._frame_rows = n
 
     def frame_end(self, with_points: Optional[bool] = None, cap: Optional[int] = None) -> FrameResult:
         """`icp_frame_end`: waits for the frame's registration alone, applies the key-frame test and enqueues the map
         update; returns the pose, the per-iteration histories, the decision and — with_points (default: as `copy_cloud`
         of `odometry_init`) — the frame's valid rows.  An `Invalid Jacobian` raises before the map is touched."""
+        return self._frame_end(self._lib.icp_frame_end, getattr(self, "_frame_cfg", None), with_points, cap)
+
+    def _frame_end(self, fn, cfg, with_points, cap) -> FrameResult:
+        """`frame_end` / `pmap_frame_end`: `fn` is the library's end call, `cfg` the sequence's configuration."""
         if with_points is None:
-            with_points = bool(getattr(self, "_frame_cfg", None) is not None and self._frame_cfg.copy_cloud)
+            with_points = bool(cfg is not None and cfg.copy_cloud)
         rows_cap = int(getattr(self, "_frame_rows", 0)) if cap is None else int(cap)
         hist = max(1, int(self.config.max_num_alignments))
         losses = (C.c_double * hist)()
@@ -910,8 +942,8 @@ class IcpContext:
         res = IcpFrameResult()
         count = C.c_int64(0)
         out = np.empty((max(rows_cap, 1), 3), np.float32) if with_points else None
-        rc = self._lib.icp_frame_end(self._h, C.byref(res), out.ctypes.data if out is not None else None, rows_cap,
-                                     C.byref(count) if with_points else None, MEM_HOST, losses, dxs)
+        rc = fn(self._h, C.byref(res), out.ctypes.data if out is not None else None, rows_cap,
+                C.byref(count) if with_points else None, MEM_HOST, losses, dxs)
         self._frame_keep = None
         try:
             self._check_registration(rc, res.reg, losses, dxs)
@@ -931,11 +963,9 @@ class IcpContext:
         projective map, frame 0).  voxel_size > 0: the grid sample in front of every [N,3] frame; targets (for [N,3] frames)
         0: the frame's rows, 1: the pixels of its vertex map; normals_kernel_size: the window of the inserted maps' normals;
         the other settings as for `odometry_init`."""
-        cfg = IcpPmapFrameConfig()
-        self._lib.icp_default_pmap_frame_config(C.byref(cfg))
-        cfg.voxel_size, cfg.threshold_trans, cfg.threshold_rot = float(voxel_size), float(threshold_trans), float(threshold_rot)
-        cfg.constant_velocity, cfg.targets, cfg.copy_cloud = int(bool(constant_velocity)), int(targets), int(bool(copy_cloud))
-        cfg.normals_kernel_size = int(normals_kernel_size)
+        cfg = _pmap_frame_config(self._lib, voxel_size=voxel_size, threshold_trans=threshold_trans, threshold_rot=threshold_rot,
+                                 constant_velocity=constant_velocity, targets=targets,
+                                 normals_kernel_size=normals_kernel_size, copy_cloud=copy_cloud)
         self._check(self._lib.icp_pmap_odometry_init(self._h, C.byref(cfg)))
         self._pframe_cfg = cfg
         self._frame_keep = None
@@ -945,69 +975,22 @@ class IcpContext:
         """`icp_pmap_frame_launch`: one frame enqueued without waiting — [N,3] float32 rows (numpy: uploaded by the library;
         a cuda tensor: used in place) or a cuda [3,H,W] / [1,3,H,W] vertex map (its pixels are the targets).  Device data
         stays untouched until `pmap_frame_end`."""
-        if isinstance(data, torch.Tensor) and data.is_cuda and data.ndim in (3, 4):
-            self._bind(data)
-            vmap = data[0] if data.ndim == 4 else data
-            if data.ndim == 4 and data.shape[0] != 1:
-                raise AssertionError("Unexpected batched data format.")
-            if vmap.shape[0] != 3:
-                raise AssertionError(f"expected a [3,H,W] vertex map, got {tuple(data.shape)}")
-            vmap = vmap if vmap.dtype == torch.float32 and vmap.is_contiguous() else vmap.to(torch.float32).contiguous()
-            if timestamps is not None:
-                raise AssertionError("timestamps go with [N,3] rows, not with a vertex map")
-            n = int(vmap.shape[1] * vmap.shape[2])
-            self._check(self._lib.icp_pmap_frame_launch(self._h, vmap.data_ptr(), n, MEM_DEVICE, FRAME_VERTEX_MAP, None,
-                                                        _pose16(init_pose) if init_pose is not None else None))
-            self._frame_keep = (vmap, None)
-            self._frame_rows = n
-            return
+        vmap = isinstance(data, torch.Tensor) and data.is_cuda and data.ndim in (3, 4)
         self._bind(data)
-        if isinstance(data, torch.Tensor) and data.is_cuda:
-            pts = data if data.dtype == torch.float32 and data.is_contiguous() else data.to(torch.float32).contiguous()
-            ts = None
-            if timestamps is not None:
-                ts = torch.as_tensor(timestamps).to(pts.device, torch.float64).reshape(-1).contiguous()
-            mem, p, tp = MEM_DEVICE, pts.data_ptr(), ts.data_ptr() if ts is not None else None
-        else:
-            pts = data.numpy() if isinstance(data, torch.Tensor) else data
-            if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.flags.c_contiguous):
-                pts = np.ascontiguousarray(pts, dtype=np.float32)
-            ts = None
-            if timestamps is not None:
-                ts = np.ascontiguousarray(np.asarray(timestamps).reshape(-1), dtype=np.float64)
-            mem, p, tp = MEM_HOST, pts.ctypes.data, ts.ctypes.data if ts is not None else None
-        if pts.ndim != 2 or pts.shape[1] != 3 or (ts is not None and ts.shape[0] != pts.shape[0]):
-            raise AssertionError(f"expected [N,3] points (and [N] timestamps) or a [3,H,W] vertex map, got {tuple(pts.shape)}")
-        n = int(pts.shape[0])
-        self._check(self._lib.icp_pmap_frame_launch(self._h, p if n else None, n, mem, FRAME_ROWS, tp if n else None,
+        if vmap and data.ndim == 4 and data.shape[0] != 1:
+            raise AssertionError("Unexpected batched data format.")
+        p, n, mem, layout, tp, keep = _frame_arrays(data, None if vmap else timestamps, vmap,
+                                                    rows_alt=" or a [3,H,W] vertex map")
+        if vmap and timestamps is not None:
+            raise AssertionError("timestamps go with [N,3] rows, not with a vertex map")
+        self._check(self._lib.icp_pmap_frame_launch(self._h, p, n, mem, layout, tp,
                                                     _pose16(init_pose) if init_pose is not None else None))
-        self._frame_keep = (pts, ts) if mem == MEM_DEVICE else None
-        self._frame_rows = n
+        self._frame_launched(keep, n, mem)
 
     def pmap_frame_end(self, with_points: Optional[bool] = None, cap: Optional[int] = None) -> FrameResult:
         """`icp_pmap_frame_end`: waits for the frame's registration alone, applies the key-frame test and enqueues the
         projective map's update; returns what `frame_end` returns (`inserted`: 1 when a vertex map was appended)."""
-        if with_points is None:
-            with_points = bool(getattr(self, "_pframe_cfg", None) is not None and self._pframe_cfg.copy_cloud)
-        rows_cap = int(getattr(self, "_frame_rows", 0)) if cap is None else int(cap)
-        hist = max(1, int(self.config.max_num_alignments))
-        losses = (C.c_double * hist)()
-        dxs = (C.c_float * (6 * hist))()
-        res = IcpFrameResult()
-        count = C.c_int64(0)
-        out = np.empty((max(rows_cap, 1), 3), np.float32) if with_points else None
-        rc = self._lib.icp_pmap_frame_end(self._h, C.byref(res), out.ctypes.data if out is not None else None, rows_cap,
-                                          C.byref(count) if with_points else None, MEM_HOST, losses, dxs)
-        self._frame_keep = None
-        try:
-            self._check_registration(rc, res.reg, losses, dxs)
-        except AssertionError as e:  # (`cap` below the frame's rows: the frame is completed all the same)
-            e.rows, e.result, e.register = int(count.value), res, self._result(res.reg, losses, dxs)
-            raise
-        first = int(res.frame_index) == 0
-        points = out[:int(count.value)] if (out is not None and not first) else None
-        return FrameResult(self._result(res.reg, losses, dxs), int(res.frame_index), bool(res.key_frame), int(res.samples),
-                           int(res.inserted), points)
+        return self._frame_end(self._lib.icp_pmap_frame_end, getattr(self, "_pframe_cfg", None), with_points, cap)
 
     # ---- aggregated world map -----------------------------------------------------------------------------------------
     def aggregated_map(self, voxel_size: float, capacity: int, max_insert_rows: int = 262144) -> "AggregatedMap":
@@ -1707,36 +1690,11 @@ class IcpBatch:
             f.skip = 1 if sk else 0
             if sk:
                 continue
-            if vmaps:
-                vm = a[0] if a.ndim == 4 else a
-                if (a.ndim == 4 and a.shape[0] != 1) or vm.shape[0] != 3:
-                    raise AssertionError(f"member {i}: expected a [3,H,W] vertex map, got {tuple(a.shape)}")
-                vm = vm if vm.dtype == torch.float32 and vm.is_contiguous() else vm.to(torch.float32).contiguous()
-                pose = _pose16(g) if g is not None else None
-                f.xyz, f.n = vm.data_ptr(), int(vm.shape[1] * vm.shape[2])
-                f.timestamps = None if t is None else torch.as_tensor(t).to(vm.device, torch.float64).data_ptr()
-                f.init_pose = C.cast(pose, C.c_void_p) if pose is not None else None
-                keep.append((vm, t, pose))
-                rows[i] = int(f.n)
-                continue
-            if on_device:
-                pts = a if a.dtype == torch.float32 and a.is_contiguous() else a.to(torch.float32).contiguous()
-                ts = None if t is None else torch.as_tensor(t).to(pts.device, torch.float64).reshape(-1).contiguous()
-                ptr, tptr = pts.data_ptr(), (ts.data_ptr() if ts is not None else None)
-            else:
-                pts = a.numpy() if isinstance(a, torch.Tensor) else a
-                if not (isinstance(pts, np.ndarray) and pts.dtype == np.float32 and pts.flags.c_contiguous):
-                    pts = np.ascontiguousarray(pts, dtype=np.float32)
-                ts = None if t is None else np.ascontiguousarray(np.asarray(t).reshape(-1), dtype=np.float64)
-                ptr, tptr = pts.ctypes.data, (ts.ctypes.data if ts is not None else None)
-            if pts.ndim != 2 or pts.shape[1] != 3 or (ts is not None and ts.shape[0] != pts.shape[0]):
-                raise AssertionError(f"member {i}: expected [N,3] points (and [N] timestamps), got {tuple(pts.shape)}")
-            n = int(pts.shape[0])
+            f.xyz, f.n, _, _, f.timestamps, arrays = _frame_arrays(a, t, vmaps, who=f"member {i}: ")
             pose = _pose16(g) if g is not None else None
-            f.xyz, f.n, f.timestamps = (ptr if n else None), n, (tptr if n else None)
             f.init_pose = C.cast(pose, C.c_void_p) if pose is not None else None
-            keep.append((pts, ts, pose))
-            rows[i] = n
+            keep.append((*arrays, pose))
+            rows[i] = int(f.n)
         mem = MEM_DEVICE if on_device else MEM_HOST
         if pmap:
             self._check(self._lib.icp_batch_pmap_frame_launch(self._h, frames, mem, FRAME_VERTEX_MAP if vmaps else FRAME_ROWS))
@@ -1747,14 +1705,7 @@ class IcpBatch:
     def pmap_odometry_init(self, **kw):
         """`icp_batch_pmap_odometry_init`: `IcpContext.pmap_odometry_init` on every member (the same keywords), every member
         checked before any is restarted."""
-        cfg = IcpPmapFrameConfig()
-        self._lib.icp_default_pmap_frame_config(C.byref(cfg))
-        conv = {"voxel_size": float, "threshold_trans": float, "threshold_rot": float, "constant_velocity": lambda v: int(bool(v)),
-                "targets": int, "normals_kernel_size": int, "copy_cloud": lambda v: int(bool(v))}
-        for k, v in kw.items():
-            if k not in conv:
-                raise TypeError(f"pmap_odometry_init() got an unexpected keyword argument {k!r}")
-            setattr(cfg, k, conv[k](v))
+        cfg = _pmap_frame_config(self._lib, **kw)
         self._check(self._lib.icp_batch_pmap_odometry_init(self._h, C.byref(cfg)))
         for c in self.contexts:
             c._pframe_cfg = cfg

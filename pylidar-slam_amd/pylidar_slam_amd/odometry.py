@@ -955,6 +955,58 @@ def _get(obj, key, default=None):
     return getattr(obj, key, default)
 
 
+def key_frame_decision(delta: np.ndarray, pose: np.ndarray, threshold_trans: float, threshold_rot: float):
+    """`__update_map`'s test (:360-380): (key frame?, delta @ pose in float32) — metres, and degrees of the Euler vector."""
+    new_delta = (delta @ pose).astype(np.float32)
+    dp = from_pose_matrix(new_delta)
+    return bool(np.linalg.norm(dp[:3]) > threshold_trans or np.linalg.norm(dp[3:]) * 180 / np.pi > threshold_rot), new_delta
+
+
+class _OneCallKdTree:
+    """`one_call_frame`: what the one-call paths need to know of the kd-tree style map."""
+    flag = "one_call_frame"
+    vertex_maps = False  # (a vertex-map tensor goes through the per-call path)
+    init, launch, end = "odometry_init", "frame_launch", "frame_end"  # on IcpContext and on IcpBatch
+    refusal = ("one_call_frame covers numpy [N, 3] and cuda [N, 3] frames: a vertex-map tensor (or a cpu tensor) goes "
+               "through the per-call path (one_call_frame=False), got ")
+    refusal_batch = ("one_call_frame covers numpy [N, 3] and cuda [N, 3] frames (all members alike): a vertex-map tensor (or a "
+                     "cpu tensor) goes through the per-call path (one_call_frame=False), got ")
+    copy_points = True  # `odometry_pc` is a copy of the rows the end call hands out
+
+    @staticmethod
+    def init_extra(member, data_dicts) -> dict:
+        # (a frame that comes padded from the device-resident grid sample is staged whatever its row count, as
+        # do_process_next_frame does: `sample_count` says so at frame 0; the batched calls stage every frame whatever it says)
+        return dict(stage_max_rows=0 if any(d.get("sample_count", None) is not None for d in data_dicts) else
+                    int(_get(member.config, "stage_insert_max_rows", 32768)))
+
+    @staticmethod
+    def record_key_frame(member, res, frame, is_vmap):
+        member.local_map._last_count = res.inserted
+
+
+class _OneCallProjective:
+    """`one_call_projective_frame`: the same of the projective local map."""
+    flag = "one_call_projective_frame"
+    vertex_maps = True
+    init, launch, end = "pmap_odometry_init", "pmap_frame_launch", "pmap_frame_end"
+    refusal = ("one_call_projective_frame covers numpy [N, 3], cuda [N, 3] and cuda [3, H, W] / [1, 3, H, W] frames: "
+               "anything else (a cpu tensor) goes through the per-call path (one_call_projective_frame=False), got ")
+    refusal_batch = ("one_call_projective_frame covers numpy [N, 3], cuda [N, 3] and cuda [3, H, W] / [1, 3, H, W] frames (all "
+                     "members alike): anything else (a cpu tensor) goes through the per-call path, got ")
+    copy_points = False  # (a view of the fresh array the end call filled: nobody else holds it)
+
+    @staticmethod
+    def init_extra(member, data_dicts) -> dict:
+        return dict(normals_kernel_size=int(member.local_map.normals_kernel_size))
+
+    @staticmethod
+    def record_key_frame(member, res, frame, is_vmap):
+        # (`get_last_frame`: a vertex map handed in is the newest stored map; for rows the library's projection is repeated
+        # here — the same pixels — behind the frame, off its critical path)
+        member.local_map._last_vmap = (frame[0] if frame.ndim == 4 else frame) if is_vmap else member.ctx.project(frame)
+
+
 class MI355XICPFrameToModel(OdometryAlgorithm):
     """Drop-in for `ICPFrameToModel` (slam/odometry/icp_odometry.py:72-381) with the kd-tree local map and the
     Gauss-Newton point-to-plane alignment, every per-point stage on the MI355X."""
@@ -1042,6 +1094,7 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
                          "one_call_projective_frame: compact_sparse_vertex_map is a schedule of the per-call path only")
             assert_debug(hasattr(self.ctx, "pmap_frame_launch"),
                          "one_call_projective_frame needs the library's projective frame calls")
+        self._one_call_kind = _OneCallKdTree if self._one_call else _OneCallProjective if self._one_call_pmap else None
 
     def init(self):  # :128-145
         super().init()
@@ -1179,24 +1232,18 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         registration alone (`icp_register_end`); the map update is enqueued from the pose without waiting for it, so it
         overlaps the caller's preparation of the next frame."""
         self.ctx.use_torch_stream()
-        if self._one_call:
+        if self._one_call_kind is not None:
             return self._one_call_next_frame(data_dict)
-        if self._one_call_pmap:
-            return self._one_call_pmap_next_frame(data_dict)
         self._read_input(data_dict)
         if self._iter == 0:
-            eye = np.eye(4, dtype=np.float32)
-            self.local_map.update(eye, new_vertex_map=self._tgt_vmap.unsqueeze(0))  # :176
-            self.relative_poses.append(eye[None])
-            self.absolute_poses.append(np.eye(4, dtype=np.float64))
-            self._iter += 1
-            return
+            self.local_map.update(np.eye(4, dtype=np.float32), new_vertex_map=self._tgt_vmap.unsqueeze(0))  # :176
+            return self._first_frame_done()
         initial_estimate = self._initial_pose(data_dict)
         targets, skip_null = self.sample_points()
         want_rows = "distorted" not in data_dict  # (:210-213: the de-skewed frame stands in for `_tgt_pc` when there is one)
         rows_ready = self._rows_event() if want_rows else None  # (recorded BEFORE the registration is enqueued)
         if self._projective:
-            params, pose, _ = self.register_new_frame(targets, initial_estimate, skip_null=skip_null)
+            self.register_new_frame(targets, initial_estimate, skip_null=skip_null)
             tgt_np_pc = self._rows_to_host(rows_ready) if want_rows else data_dict["distorted"]
         else:
             # the frame goes into the map right after its registration (:229-231): its valid rows are compacted and counted
@@ -1215,84 +1262,50 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
             if self._tgt_vmap is None:  # (deferred in _read_input: enqueued behind the registration, off its critical path)
                 self._tgt_vmap = self.ctx.project(self._tgt_pc)
             tgt_np_pc = self._rows_to_host(rows_ready) if want_rows else data_dict["distorted"]  # GPU busy meanwhile
-            res = self.ctx.register_end()  # raises before the map is touched (:286)
-            self.last_result = res
-            params, pose = res.params, res.pose
-        self.__update_map(pose)
+            self.last_result = self.ctx.register_end()  # raises before the map is touched (:286)
+        self.__update_map(self.last_result.pose)
+        self._frame_done(data_dict, self.last_result, tgt_np_pc,
+                         self._tgt_pc if (want_rows and self._tgt_pc.is_cuda and not self._pc_is_pixels) else None)
+
+    # ---- the ends of a frame every path shares ---------------------------------------------------------------------------
+    def _first_frame_done(self):
+        """Frame 0 is in the map (:176-181): the identity opens both pose chains; nothing is written to the dict."""
+        self.relative_poses.append(np.eye(4, dtype=np.float32)[None])
+        self.absolute_poses.append(np.eye(4, dtype=np.float64))
+        self._iter += 1
+
+    def _key_frame(self, pose: np.ndarray, decided=None) -> bool:
+        """`__update_map`'s decision for `pose` (:360-380) — `decided`: the library has taken it — and what it leaves in
+        `_delta_since_map_update`."""
+        if decided is None:
+            key_frame, new_delta = key_frame_decision(self._delta_since_map_update, pose, self._register_threshold_trans,
+                                                      self._register_threshold_rot)
+        else:
+            key_frame = bool(decided)
+            new_delta = None if key_frame else (self._delta_since_map_update @ pose).astype(np.float32)
+        self._delta_since_map_update = np.eye(4, dtype=np.float32) if key_frame else new_delta
+        return key_frame
+
+    def _frame_done(self, data_dict: dict, res: RegisterResult, odometry_pc, device_rows=None):
+        """A registered frame is in the map: the pose chains (:200-202), the dict's outputs (:243-244), the aggregated map."""
+        self.last_result = res
+        pose = res.pose
         self.relative_poses.append(pose[None].copy())
-        self.absolute_poses.append(self.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64),
-                                                                                 np.float64)))  # :200-202
-        data_dict[self.pointcloud_key()] = tgt_np_pc  # :243
-        data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
-        self._aggregate(data_dict, self._tgt_pc if (want_rows and self._tgt_pc.is_cuda and not self._pc_is_pixels) else None)
+        self.absolute_poses.append(self.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
+        data_dict[self.pointcloud_key()] = odometry_pc
+        data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()
+        self._aggregate(data_dict, device_rows)
         self._iter += 1
 
     def _one_call_next_frame(self, data_dict: dict):
-        """`one_call_frame`: the frame through icp_frame_launch + icp_frame_end.  The library uploads a numpy frame, projects,
-        stages, registers from `init_rpose`, applies the key-frame test of `__update_map` and updates the map; what stays
-        here is the pose chain and the outputs written to the dict.  The initial guess stays the dict's `init_rpose` (the
-        initialisation is a module of its own in the reference, slam/slam.py:126-140), handed over explicitly with every frame:
-        the library's own constant-velocity mode (the guess read on the device) is for callers without such a module."""
-        key = self.config.data_key
-        assert_debug(key in data_dict, f"Could not find the key `{key}` in the input dictionary.\n"
-                                       f"With keys : {data_dict.keys()}). Set the parameter "
-                                       f"`slam.odometry.data_key` to the desired key")
-        data = data_dict[key]
-        is_numpy = isinstance(data, np.ndarray)
-        assert_debug(is_numpy or (isinstance(data, torch.Tensor) and data.is_cuda and data.ndim == 2),
-                     "one_call_frame covers numpy [N, 3] and cuda [N, 3] frames: a vertex-map tensor (or a cpu tensor) goes "
-                     "through the per-call path (one_call_frame=False), got "
-                     f"{type(data).__name__} {tuple(getattr(data, 'shape', ()))}")
-        assert_debug(data.ndim == 2 and data.shape[1] == 3, f"expected [N, 3], got {tuple(data.shape)}")
-        if is_numpy:
-            self._sample_pointcloud = True  # sticky (:330)
-        targets = 0 if self._sample_pointcloud else 1  # sample_points :301-308
-        want_rows = "distorted" not in data_dict  # (:210-213)
-        # (`odometry_pc` of a numpy frame is made from the host rows the caller handed over, as on the per-call path: nothing
-        # to copy back; a tensor frame's valid rows come back from the library, copied beside the registration)
-        from_device = want_rows and not is_numpy
-        if self._iter == 0:
-            self.ctx.odometry_init(voxel_size=0.0, threshold_trans=self._register_threshold_trans,
-                                   threshold_rot=self._register_threshold_rot, constant_velocity=False, targets=targets,
-                                   copy_cloud=from_device,
-                                   # (a frame that comes padded from the device-resident grid sample is staged whatever its
-                                   # row count, as do_process_next_frame does: `sample_count` says so at frame 0)
-                                   stage_max_rows=0 if data_dict.get("sample_count", None) is not None else
-                                   int(_get(self.config, "stage_insert_max_rows", 32768)))
-            self._one_call_targets = targets
-        assert_debug(targets == self._one_call_targets, "one_call_frame: numpy and tensor frames were mixed within one "
-                                                        "sequence (the targets of a sequence are its rows or its pixels)")
-        self._host_rows = None
-        if is_numpy:
-            self._host_rows = data if data.dtype == np.float32 and data.flags.c_contiguous else \
-                np.ascontiguousarray(data, dtype=np.float32)
-        self.ctx.frame_launch(self._host_rows if is_numpy else data, None,
-                              self._initial_pose(data_dict) if self._iter > 0 else None)
-        tgt_np_pc = self._rows_to_host(None) if (want_rows and is_numpy and self._iter > 0) else None  # GPU busy meanwhile
-        res = self.ctx.frame_end(with_points=from_device and self._iter > 0)  # raises before the map is touched (:286)
-        if self._iter == 0:
-            self.relative_poses.append(np.eye(4, dtype=np.float32)[None])
-            self.absolute_poses.append(np.eye(4, dtype=np.float64))
-            self._iter += 1
-            return
-        self.last_result = res.register
-        pose, params = res.register.pose, res.register.params
-        self.relative_poses.append(pose[None].copy())
-        self.absolute_poses.append(self.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64),
-                                                                                 np.float64)))  # :200-202
-        if want_rows and not is_numpy:
-            tgt_np_pc = res.points.copy()
-        data_dict[self.pointcloud_key()] = tgt_np_pc if want_rows else data_dict["distorted"]  # :243
-        data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
-        self._aggregate(data_dict, data if (want_rows and not is_numpy and data.ndim == 2) else None)
-        self._iter += 1
-
-    def _one_call_pmap_next_frame(self, data_dict: dict):
-        """`one_call_projective_frame`: the frame through icp_pmap_frame_launch + icp_pmap_frame_end.  The library uploads a
-        numpy frame, projects (or transposes a vertex map into target rows), compacts and copies out `odometry_pc`, registers
-        against the projective map from `init_rpose`, applies the key-frame test of `__update_map` and updates the map; what
-        stays here is the pose chain and the outputs written to the dict.  As on `_one_call_next_frame` the guess is the
-        dict's `init_rpose`, handed over with every frame."""
+        """`one_call_frame` / `one_call_projective_frame`: the frame through ONE pair of library calls (icp_frame_launch +
+        icp_frame_end, or icp_pmap_frame_launch + icp_pmap_frame_end; `_OneCallKdTree` / `_OneCallProjective` say what differs).
+        The library uploads a numpy frame, projects (or transposes a vertex map into target rows), stages, copies out
+        `odometry_pc`, registers from `init_rpose`, applies the key-frame test of `__update_map` and updates the map; what
+        stays here is the pose chain and the outputs written to the dict.  The initial guess stays the dict's `init_rpose`
+        (the initialisation is a module of its own in the reference, slam/slam.py:126-140), handed over explicitly with every
+        frame: the library's own constant-velocity mode (the guess read on the device) is for callers without such a module."""
+        kind = self._one_call_kind
         key = self.config.data_key
         assert_debug(key in data_dict, f"Could not find the key `{key}` in the input dictionary.\n"
                                        f"With keys : {data_dict.keys()}). Set the parameter "
@@ -1300,11 +1313,9 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         data = data_dict[key]
         is_numpy = isinstance(data, np.ndarray)
         is_cuda = isinstance(data, torch.Tensor) and data.is_cuda
-        is_vmap = is_cuda and data.ndim in (3, 4)
-        assert_debug(is_numpy or (is_cuda and data.ndim in (2, 3, 4)),
-                     "one_call_projective_frame covers numpy [N, 3], cuda [N, 3] and cuda [3, H, W] / [1, 3, H, W] frames: "
-                     "anything else (a cpu tensor) goes through the per-call path (one_call_projective_frame=False), got "
-                     f"{type(data).__name__} {tuple(getattr(data, 'shape', ()))}")
+        is_vmap = kind.vertex_maps and is_cuda and data.ndim in (3, 4)
+        assert_debug(is_numpy or is_vmap or (is_cuda and data.ndim == 2),
+                     kind.refusal + f"{type(data).__name__} {tuple(getattr(data, 'shape', ()))}")
         if is_vmap:
             assert_debug(data.ndim == 3 or data.shape[0] == 1, "Unexpected batched data format.")
             assert_debug(data.shape[-3] == 3 and tuple(data.shape[-2:]) == (int(self.projector.height), int(self.projector.width)),
@@ -1315,46 +1326,41 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
             self._sample_pointcloud = True  # sticky (:330)
         targets = 0 if self._sample_pointcloud else 1  # sample_points :301-308 (a vertex map's targets are its pixels anyway)
         want_rows = "distorted" not in data_dict  # (:210-213)
+        # (`odometry_pc` of a numpy frame is made from the host rows the caller handed over, as on the per-call path: nothing
+        # to copy back; a tensor frame's valid rows come back from the library, copied beside the registration)
         from_device = want_rows and not is_numpy
-        if self._iter == 0:
-            self.ctx.pmap_odometry_init(voxel_size=0.0, threshold_trans=self._register_threshold_trans,
-                                        threshold_rot=self._register_threshold_rot, constant_velocity=False, targets=targets,
-                                        normals_kernel_size=int(self.local_map.normals_kernel_size), copy_cloud=from_device)
+        first = self._iter == 0
+        if first:
+            getattr(self.ctx, kind.init)(voxel_size=0.0, threshold_trans=self._register_threshold_trans,
+                                         threshold_rot=self._register_threshold_rot, constant_velocity=False, targets=targets,
+                                         copy_cloud=from_device, **kind.init_extra(self, [data_dict]))
             self._one_call_targets = targets
         assert_debug(is_vmap or targets == self._one_call_targets,
-                     "one_call_projective_frame: numpy and tensor frames were mixed within one sequence (the targets of a "
+                     f"{kind.flag}: numpy and tensor frames were mixed within one sequence (the targets of a "
                      "sequence are its rows or its pixels)")
         self._host_rows = None
         if is_numpy:
             self._host_rows = data if data.dtype == np.float32 and data.flags.c_contiguous else \
                 np.ascontiguousarray(data, dtype=np.float32)
-        self.ctx.pmap_frame_launch(self._host_rows if is_numpy else data, None,
-                                   self._initial_pose(data_dict) if self._iter > 0 else None)
-        tgt_np_pc = self._rows_to_host(None) if (want_rows and is_numpy and self._iter > 0) else None  # GPU busy meanwhile
-        res = self.ctx.pmap_frame_end(with_points=from_device and self._iter > 0)  # raises before the map is touched (:286)
+        frame = self._host_rows if is_numpy else data
+        getattr(self.ctx, kind.launch)(frame, None, None if first else self._initial_pose(data_dict))
+        host_pc = self._rows_to_host(None) if (want_rows and is_numpy and not first) else None  # GPU busy meanwhile
+        res = getattr(self.ctx, kind.end)(with_points=from_device and not first)  # raises before the map is touched (:286)
+        self._one_call_frame_done(kind, data_dict, res, frame, is_vmap, want_rows, host_pc)
+
+    def _one_call_frame_done(self, kind, data_dict: dict, res, frame, is_vmap: bool, want_rows: bool, host_pc):
+        """What a one-call frame leaves behind in the plugin (`MI355XICPFrameToModelBatch`: per member).  `frame`: what was
+        launched; `host_pc`: `odometry_pc` where it was made from a numpy frame's own rows."""
         if res.key_frame:
-            # (`get_last_frame`: a vertex map handed in is the newest stored map; for rows the library's projection is repeated
-            # here — the same pixels — behind the frame, off its critical path)
-            self.local_map._last_vmap = (data[0] if data.ndim == 4 else data) if is_vmap else \
-                self.ctx.project(self._host_rows if is_numpy else data)
+            kind.record_key_frame(self, res, frame, is_vmap)
         if self._iter == 0:
-            self.relative_poses.append(np.eye(4, dtype=np.float32)[None])
-            self.absolute_poses.append(np.eye(4, dtype=np.float64))
-            self._iter += 1
-            return
-        self.last_result = res.register
-        pose, params = res.register.pose, res.register.params
-        self._delta_since_map_update = np.eye(4, dtype=np.float32) if res.key_frame else \
-            (self._delta_since_map_update @ pose).astype(np.float32)
-        self.relative_poses.append(pose[None].copy())
-        self.absolute_poses.append(self.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64),
-                                                                                 np.float64)))  # :200-202
-        if want_rows and not is_numpy:
-            tgt_np_pc = res.points  # (a view of the fresh array the call filled: nobody else holds it)
-        data_dict[self.pointcloud_key()] = tgt_np_pc if want_rows else data_dict["distorted"]  # :243
-        data_dict[self.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
-        self._aggregate(data_dict, data if (want_rows and not is_numpy and data.ndim == 2) else None)
-        self._iter += 1
+            return self._first_frame_done()
+        self._key_frame(res.register.pose, decided=res.key_frame)
+        from_device = want_rows and not isinstance(frame, np.ndarray)
+        if from_device:
+            host_pc = res.points.copy() if kind.copy_points else res.points
+        self._frame_done(data_dict, res.register, host_pc if want_rows else data_dict["distorted"],
+                         frame if (from_device and frame.ndim == 2) else None)
 
     # ---- host <-> device traffic of a frame, kept off the critical path ----------------------------------------------
     def _upload(self, rows: np.ndarray) -> torch.Tensor:
@@ -1434,10 +1440,9 @@ class MI355XICPFrameToModel(OdometryAlgorithm):
         return self._pin_out[:n].numpy().copy()
 
     def __update_map(self, new_rpose: np.ndarray):  # :360-380
-        new_delta = (self._delta_since_map_update @ new_rpose).astype(np.float32)
-        dp = from_pose_matrix(new_delta)
-        if np.linalg.norm(dp[:3]) > self._register_threshold_trans or \
-                np.linalg.norm(dp[3:]) * 180 / np.pi > self._register_threshold_rot:
+        key_frame, new_delta = key_frame_decision(self._delta_since_map_update, new_rpose, self._register_threshold_trans,
+                                                  self._register_threshold_rot)
+        if key_frame:
             if self._projective:  # the projective map takes the vertex map (local_map.py:122-131)
                 self.local_map.update(new_rpose, new_vertex_map=self._tgt_vmap.unsqueeze(0))
                 self._delta_since_map_update = np.eye(4, dtype=np.float32)
@@ -1508,6 +1513,7 @@ class MI355XICPFrameToModelBatch:
         if self._one_call_pmap:
             assert_debug(hasattr(self.batch, "pmap_frame_launch"),
                          "one_call_projective_frame needs the library's batched projective frame calls")
+        self._one_call_kind = m0._one_call_kind
 
     def __len__(self):
         return len(self.members)
@@ -1529,98 +1535,22 @@ class MI355XICPFrameToModelBatch:
         its initial estimate under `init_rpose` as for the single plugin); fills `odometry_pose` and `odometry_pc` of every
         dict, as MI355XICPFrameToModel.process_next_frame does."""
         beginning = time.time()
-        if self._one_call:
+        if self._one_call_kind is not None:
             self._process_one_call(data_dicts)
-        elif self._one_call_pmap:
-            self._process_one_call_pmap(data_dicts)
         else:
             self._process(data_dicts)
         self.elapsed.append(time.time() - beginning)
 
     def _process_one_call(self, data_dicts):
-        """`one_call_frame`: the step through icp_batch_frame_launch + icp_batch_frame_end — per member what
-        `MI355XICPFrameToModel._one_call_next_frame` does with icp_frame_launch + icp_frame_end: the library uploads numpy
-        frames (ONE pinned buffer and ONE copy for all members), projects, stages, registers from every dict's `init_rpose`,
-        applies the key-frame tests and updates the maps; what stays here are the pose chains and the dicts' outputs.  numpy
-        [N, 3] frames (not accepted on the per-call path) and cuda [N, 3] frames.  A member whose registration fails raises
-        `InvalidJacobianError` after the other members have completed their frame (their dicts and pose lists are filled)."""
-        members = self.members
-        assert_debug(len(data_dicts) == len(members), f"expected {len(members)} frames, got {len(data_dicts)}")
-        key = self.config.data_key
-        for d in data_dicts:
-            assert_debug(key in d, f"Could not find the key `{key}` in the input dictionary.")
-        frames = [d[key] for d in data_dicts]
-        is_numpy = all(isinstance(f, np.ndarray) for f in frames)
-        assert_debug(is_numpy or all(isinstance(f, torch.Tensor) and f.is_cuda and f.ndim == 2 for f in frames),
-                     "one_call_frame covers numpy [N, 3] and cuda [N, 3] frames (all members alike): a vertex-map tensor (or a "
-                     "cpu tensor) goes through the per-call path (one_call_frame=False), got "
-                     f"{[(type(f).__name__, tuple(getattr(f, 'shape', ()))) for f in frames]}")
-        for f in frames:
-            assert_debug(f.ndim == 2 and f.shape[1] == 3, f"expected [N, 3], got {tuple(f.shape)}")
-        if is_numpy:
-            for m in members:
-                m._sample_pointcloud = True  # sticky (:330)
-        targets = 0 if members[0]._sample_pointcloud else 1  # sample_points :301-308
-        want = ["distorted" not in d for d in data_dicts]  # (:210-213)
-        first = self._iter == 0
-        if first:
-            self.batch.use_torch_stream()
-            self.batch.odometry_init(voxel_size=0.0, threshold_trans=members[0]._register_threshold_trans,
-                                     threshold_rot=members[0]._register_threshold_rot, constant_velocity=False,
-                                     targets=targets, copy_cloud=any(want) and not is_numpy,
-                                     # (`_one_call_next_frame`'s rule; the batched calls stage every frame whatever it says)
-                                     stage_max_rows=0 if any(d.get("sample_count", None) is not None for d in data_dicts) else
-                                     int(_get(self.config, "stage_insert_max_rows", 32768)))
-            self._one_call_targets = targets
-        assert_debug(targets == self._one_call_targets, "one_call_frame: numpy and tensor frames were mixed within one "
-                                                        "sequence (the targets of a sequence are its rows or its pixels)")
-        if is_numpy:
-            frames = [f if f.dtype == np.float32 and f.flags.c_contiguous else np.ascontiguousarray(f, dtype=np.float32)
-                      for f in frames]
-        else:
-            self.batch.use_torch_stream()
-        self.batch.frame_launch(frames, None, None if first else [m._initial_pose(d) for m, d in zip(members, data_dicts)])
-        pcs = [None] * len(members)
-        if is_numpy and not first:  # (`odometry_pc` of a numpy frame is made from the host rows: GPU busy meanwhile)
-            for b, (m, f, w) in enumerate(zip(members, frames, want)):
-                m._host_rows = f
-                pcs[b] = m._rows_to_host(None) if w else None
-        error = None
-        try:
-            results = self.batch.frame_end(with_points=[w and not is_numpy and not first for w in want])
-        except InvalidJacobianError as e:  # (raised behind the step: the healthy members have completed their frame)
-            error, results = e, e.results
-        for b, (m, res, d) in enumerate(zip(members, results, data_dicts)):
-            if res is None:
-                continue
-            if first:
-                m.relative_poses.append(np.eye(4, dtype=np.float32)[None])
-                m.absolute_poses.append(np.eye(4, dtype=np.float64))
-                m._iter += 1
-                continue
-            m.last_result = res.register
-            pose, params = res.register.pose, res.register.params
-            m._delta_since_map_update = np.eye(4, dtype=np.float32) if res.key_frame else \
-                (m._delta_since_map_update @ pose).astype(np.float32)
-            if res.key_frame:
-                m.local_map._last_count = res.inserted
-            m.relative_poses.append(pose[None].copy())
-            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64), np.float64)))
-            if want[b] and not is_numpy:
-                pcs[b] = res.points.copy()
-            d[m.pointcloud_key()] = pcs[b] if want[b] else d["distorted"]  # :243
-            d[m.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
-            m._aggregate(d, frames[b] if (want[b] and not is_numpy and frames[b].ndim == 2) else None)
-            m._iter += 1
-        self._iter += 1
-        if error is not None:
-            raise error
-
-    def _process_one_call_pmap(self, data_dicts):
-        """`one_call_projective_frame`: the step through icp_batch_pmap_frame_launch + icp_batch_pmap_frame_end — per member what
-        `MI355XICPFrameToModel._one_call_pmap_next_frame` does with the single calls.  numpy [N, 3], cuda [N, 3] or cuda
-        [3, H, W] / [1, 3, H, W] frames, all members alike.  A member whose registration fails raises `InvalidJacobianError`
-        after the other members have completed their frame."""
+        """`one_call_frame` / `one_call_projective_frame`: the step through ONE pair of batched library calls
+        (icp_batch_frame_launch + icp_batch_frame_end, or their icp_batch_pmap_ counterparts) — per member what
+        `MI355XICPFrameToModel._one_call_next_frame` does with the single calls: the library uploads numpy frames (ONE pinned
+        buffer and ONE copy for all members), projects, stages, registers from every dict's `init_rpose`, applies the key-frame
+        tests and updates the maps; what stays here are the pose chains and the dicts' outputs.  numpy [N, 3] frames (not
+        accepted on the per-call path), cuda [N, 3] frames and — projective map — cuda [3, H, W] / [1, 3, H, W] frames, all
+        members alike.  A member whose registration fails raises `InvalidJacobianError` after the other members have completed
+        their frame (their dicts and pose lists are filled)."""
+        kind = self._one_call_kind
         members = self.members
         assert_debug(len(data_dicts) == len(members), f"expected {len(members)} frames, got {len(data_dicts)}")
         key = self.config.data_key
@@ -1629,11 +1559,9 @@ class MI355XICPFrameToModelBatch:
         frames = [d[key] for d in data_dicts]
         is_numpy = all(isinstance(f, np.ndarray) for f in frames)
         is_cuda = all(isinstance(f, torch.Tensor) and f.is_cuda for f in frames)
-        is_vmap = is_cuda and all(f.ndim in (3, 4) for f in frames)
+        is_vmap = kind.vertex_maps and is_cuda and all(f.ndim in (3, 4) for f in frames)
         assert_debug(is_numpy or is_vmap or (is_cuda and all(f.ndim == 2 for f in frames)),
-                     "one_call_projective_frame covers numpy [N, 3], cuda [N, 3] and cuda [3, H, W] / [1, 3, H, W] frames (all "
-                     "members alike): anything else (a cpu tensor) goes through the per-call path, got "
-                     f"{[(type(f).__name__, tuple(getattr(f, 'shape', ()))) for f in frames]}")
+                     kind.refusal_batch + f"{[(type(f).__name__, tuple(getattr(f, 'shape', ()))) for f in frames]}")
         if not is_vmap:
             for f in frames:
                 assert_debug(f.ndim == 2 and f.shape[1] == 3, f"expected [N, 3], got {tuple(f.shape)}")
@@ -1645,20 +1573,21 @@ class MI355XICPFrameToModelBatch:
         first = self._iter == 0
         if first:
             self.batch.use_torch_stream()
-            self.batch.pmap_odometry_init(voxel_size=0.0, threshold_trans=members[0]._register_threshold_trans,
-                                          threshold_rot=members[0]._register_threshold_rot, constant_velocity=False,
-                                          targets=targets, normals_kernel_size=int(members[0].local_map.normals_kernel_size),
-                                          copy_cloud=any(want) and not is_numpy)
+            getattr(self.batch, kind.init)(voxel_size=0.0, threshold_trans=members[0]._register_threshold_trans,
+                                           threshold_rot=members[0]._register_threshold_rot, constant_velocity=False,
+                                           targets=targets, copy_cloud=any(want) and not is_numpy,
+                                           **kind.init_extra(members[0], data_dicts))
             self._one_call_targets = targets
         assert_debug(is_vmap or targets == self._one_call_targets,
-                     "one_call_projective_frame: numpy and tensor frames were mixed within one sequence (the targets of a "
+                     f"{kind.flag}: numpy and tensor frames were mixed within one sequence (the targets of a "
                      "sequence are its rows or its pixels)")
         if is_numpy:
             frames = [f if f.dtype == np.float32 and f.flags.c_contiguous else np.ascontiguousarray(f, dtype=np.float32)
                       for f in frames]
         else:
             self.batch.use_torch_stream()
-        self.batch.pmap_frame_launch(frames, None, None if first else [m._initial_pose(d) for m, d in zip(members, data_dicts)])
+        getattr(self.batch, kind.launch)(frames, None,
+                                         None if first else [m._initial_pose(d) for m, d in zip(members, data_dicts)])
         pcs = [None] * len(members)
         if is_numpy and not first:  # (`odometry_pc` of a numpy frame is made from the host rows: GPU busy meanwhile)
             for b, (m, f, w) in enumerate(zip(members, frames, want)):
@@ -1666,31 +1595,12 @@ class MI355XICPFrameToModelBatch:
                 pcs[b] = m._rows_to_host(None) if w else None
         error = None
         try:
-            results = self.batch.pmap_frame_end(with_points=[w and not is_numpy and not first for w in want])
+            results = getattr(self.batch, kind.end)(with_points=[w and not is_numpy and not first for w in want])
         except InvalidJacobianError as e:  # (raised behind the step: the healthy members have completed their frame)
             error, results = e, e.results
-        for b, (m, res, d, f) in enumerate(zip(members, results, data_dicts, frames)):
-            if res is None:
-                continue
-            if res.key_frame:
-                m.local_map._last_vmap = (f[0] if f.ndim == 4 else f) if is_vmap else m.ctx.project(f)
-            if first:
-                m.relative_poses.append(np.eye(4, dtype=np.float32)[None])
-                m.absolute_poses.append(np.eye(4, dtype=np.float64))
-                m._iter += 1
-                continue
-            m.last_result = res.register
-            pose, params = res.register.pose, res.register.params
-            m._delta_since_map_update = np.eye(4, dtype=np.float32) if res.key_frame else \
-                (m._delta_since_map_update @ pose).astype(np.float32)
-            m.relative_poses.append(pose[None].copy())
-            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(params.astype(np.float64), np.float64)))
-            if want[b] and not is_numpy:
-                pcs[b] = res.points  # (a view of the fresh array the call filled: nobody else holds it)
-            d[m.pointcloud_key()] = pcs[b] if want[b] else d["distorted"]  # :243
-            d[m.relative_pose_key()] = pose.reshape(4, 4).copy()  # :244
-            m._aggregate(d, frames[b] if (want[b] and not is_numpy and frames[b].ndim == 2) else None)
-            m._iter += 1
+        for m, res, d, f, w, pc in zip(members, results, data_dicts, frames, want, pcs):
+            if res is not None:
+                m._one_call_frame_done(kind, d, res, f, is_vmap, w, pc)
         self._iter += 1
         if error is not None:
             raise error
@@ -1719,12 +1629,9 @@ class MI355XICPFrameToModelBatch:
             self._process_projective(data_dicts)
             return
         if self._iter == 0:
-            eye = np.eye(4, dtype=np.float32)
             for m in members:  # :176
-                m.local_map.update(eye, new_vertex_map=m._tgt_vmap.unsqueeze(0))
-                m.relative_poses.append(eye[None])
-                m.absolute_poses.append(np.eye(4, dtype=np.float64))
-                m._iter += 1
+                m.local_map.update(np.eye(4, dtype=np.float32), new_vertex_map=m._tgt_vmap.unsqueeze(0))
+                m._first_frame_done()
             self._iter += 1
             return
         inits = [m._initial_pose(d) for m, d in zip(members, data_dicts)]
@@ -1739,25 +1646,12 @@ class MI355XICPFrameToModelBatch:
         pcs = [m._rows_to_host(r) if w else d["distorted"] for m, r, w, d in zip(members, ready, want, data_dicts)]
         results = self.batch.register_end()  # raises before a map is touched (:286)
         # the key-frame decisions, each with __update_map's own arithmetic (:360-380)
-        insert = []
-        for m, res in zip(members, results):
-            new_delta = (m._delta_since_map_update @ res.pose).astype(np.float32)
-            dp = from_pose_matrix(new_delta)
-            key_frame = bool(np.linalg.norm(dp[:3]) > m._register_threshold_trans or
-                             np.linalg.norm(dp[3:]) * 180 / np.pi > m._register_threshold_rot)
-            m._delta_since_map_update = np.eye(4, dtype=np.float32) if key_frame else new_delta
-            insert.append(key_frame)
+        insert = [m._key_frame(res.pose) for m, res in zip(members, results)]
         inserted = self.batch.map_update_staged(insert, [res.pose for res in results])
         for m, res, d, pc, ins, key_frame in zip(members, results, data_dicts, pcs, inserted, insert):
-            m.last_result = res
             if key_frame:
                 m.local_map._last_count = ins
-            m.relative_poses.append(res.pose[None].copy())
-            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
-            d[m.pointcloud_key()] = pc  # :243
-            d[m.relative_pose_key()] = res.pose.reshape(4, 4).copy()  # :244
-            m._aggregate(d, m._tgt_pc if ("distorted" not in d and m._tgt_pc.is_cuda and not m._pc_is_pixels) else None)
-            m._iter += 1
+            m._frame_done(d, res, pc, m._tgt_pc if ("distorted" not in d and m._tgt_pc.is_cuda and not m._pc_is_pixels) else None)
         self._iter += 1
 
     def _process_projective(self, data_dicts):
@@ -1765,13 +1659,10 @@ class MI355XICPFrameToModelBatch:
         members = self.members
         ks = members[0].local_map.normals_kernel_size
         if self._iter == 0:  # :176 — every member's first vertex map, one batched insertion
-            eye = np.eye(4, dtype=np.float32)
-            self.batch.pmap_update([eye] * len(members), [m._tgt_vmap for m in members], ks)
+            self.batch.pmap_update([np.eye(4, dtype=np.float32)] * len(members), [m._tgt_vmap for m in members], ks)
             for m in members:
                 m.local_map._last_vmap = m._tgt_vmap
-                m.relative_poses.append(eye[None])
-                m.absolute_poses.append(np.eye(4, dtype=np.float64))
-                m._iter += 1
+                m._first_frame_done()
             self._iter += 1
             return
         inits = [m._initial_pose(d) for m, d in zip(members, data_dicts)]
@@ -1784,23 +1675,10 @@ class MI355XICPFrameToModelBatch:
         pcs = [m._rows_to_host(r) if w else d["distorted"] for m, r, w, d in zip(members, ready, want, data_dicts)]
         results = self.batch.register_end()  # raises before a map is touched (:286)
         # the key-frame decisions, each with __update_map's own arithmetic (:360-380)
-        vmaps = []
-        for m, res in zip(members, results):
-            new_delta = (m._delta_since_map_update @ res.pose).astype(np.float32)
-            dp = from_pose_matrix(new_delta)
-            key_frame = bool(np.linalg.norm(dp[:3]) > m._register_threshold_trans or
-                             np.linalg.norm(dp[3:]) * 180 / np.pi > m._register_threshold_rot)
-            m._delta_since_map_update = np.eye(4, dtype=np.float32) if key_frame else new_delta
-            vmaps.append(m._tgt_vmap if key_frame else None)
+        vmaps = [m._tgt_vmap if m._key_frame(res.pose) else None for m, res in zip(members, results)]
         self.batch.pmap_update([res.pose for res in results], vmaps, ks)
         for m, res, d, pc, vm in zip(members, results, data_dicts, pcs, vmaps):
-            m.last_result = res
             if vm is not None:
                 m.local_map._last_vmap = vm
-            m.relative_poses.append(res.pose[None].copy())
-            m.absolute_poses.append(m.absolute_poses[-1].dot(build_pose_matrix(res.params.astype(np.float64), np.float64)))
-            d[m.pointcloud_key()] = pc  # :243
-            d[m.relative_pose_key()] = res.pose.reshape(4, 4).copy()  # :244
-            m._aggregate(d, m._tgt_pc if ("distorted" not in d and m._tgt_pc.is_cuda and not m._pc_is_pixels) else None)
-            m._iter += 1
+            m._frame_done(d, res, pc, m._tgt_pc if ("distorted" not in d and m._tgt_pc.is_cuda and not m._pc_is_pixels) else None)
         self._iter += 1

@@ -314,6 +314,41 @@ def test_refusals_change_nothing(torch_cuda):
         batch.odometry_init()
 
 
+def test_one_pending_step_per_batch_whatever_its_kind(torch_cuda):
+    """A batch over a projective and a kd-tree member: while a step of one kind awaits its end, a launch of the other kind is
+    refused with nothing changed — the pending step is then ended by its own end call, and the other kind runs."""
+    torch = torch_cuda
+    from pylidar_slam_amd.engine import IcpBatch
+    v = _vmaps(torch, 4100)
+    rows = [torch.from_numpy(s).cuda() for s in _scans(4211)[:2]]
+    pm, kd = _ctx(), _ctx()
+    pm.pmap_odometry_init(**INIT)
+    kd.odometry_init(targets=0)
+    mixed = IcpBatch([pm, kd])
+    mixed.pmap_frame_launch([v[0], None], skip=[False, True])
+    with pytest.raises(AssertionError, match=r"icp_batch_frame_launch: a projective step of this batch awaits "
+                                             r"icp_batch_pmap_frame_end \(nothing was changed\)"):
+        mixed.frame_launch([None, rows[0]], skip=[True, False])
+    with pytest.raises(AssertionError, match="no step launched"):
+        mixed.frame_end()
+    first = mixed.pmap_frame_end()
+    assert first[0].frame_index == 0 and first[1] is None
+    mixed.frame_launch([None, rows[0]], skip=[True, False])
+    with pytest.raises(AssertionError, match=r"icp_batch_pmap_frame_launch: a kd-tree step of this batch awaits "
+                                             r"icp_batch_frame_end \(nothing was changed\)"):
+        mixed.pmap_frame_launch([v[1], None], skip=[False, True])
+    first = mixed.frame_end()
+    assert first[0] is None and first[1].frame_index == 0
+    # both members go on from where they stood
+    mixed.pmap_frame_launch([v[1], None], skip=[False, True])
+    assert mixed.pmap_frame_end()[0].frame_index == 1
+    mixed.frame_launch([None, rows[1]], skip=[True, False])
+    assert mixed.frame_end()[1].frame_index == 1
+    mixed.close()
+    for c in (pm, kd):
+        c.close()
+
+
 # ---- the plugins' flag ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["vmap", "rows_device", "rows_host"])
 def test_batch_plugin_flag_equals_the_single_plugin_without_it(torch_cuda, kind):
