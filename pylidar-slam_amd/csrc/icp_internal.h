@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -522,7 +523,7 @@ struct icp_ctx {
     bool lead_latched = false;         // lead launches for the registration in progress: decided once, in register_begin
     int tail_capacity = -1;            // workgroups of the tail's shape the device holds at once (-1: not asked yet)
     int handoff_fallbacks = 0;         // registrations finished on per-iteration launches behind a timed-out hand-off
-    bool batch_hold = false;           // a batched registration of this context holds iterations back (api.hip: icp_batch): individual entry points refuse
+    bool batch_hold = false;           // a batched registration of this context holds iterations back (batch.hip: icp_batch): individual entry points refuse
     bool counted_registering = false;  // this context is counted among the registering contexts of its device (api.hip)
     bool update_behind_registration = false;  // a pose-only map update by the device pose is enqueued behind an uncollected registration
     icp::DeviceBuffer tail_rows;       // tagged super-rows of the tail: [rows][NEQ][2] granules of 8 bytes
@@ -617,7 +618,7 @@ struct icp_ctx {
     struct icp_pmap_frame_loop* pframe = nullptr;  // created by icp_pmap_odometry_init, released by icp_destroy
 };
 
-// ---- B sequences per launch (api.hip: icp_batch_*)
+// ---- B sequences per launch (batch.hip: icp_batch_*)
 struct icp_batch {
     std::vector<icp_ctx*> members;
     std::string error;
@@ -798,7 +799,7 @@ int pmap_store_slot(icp_ctx* ctx, int slot, const float* vmap_dev, const float* 
 int pmap_build(icp_ctx* ctx);
 int pmap_iterate(icp_ctx* ctx, int* blocks_out);
 int pmap_associate(icp_ctx* ctx, const float* xyz_dev, int64_t n, float* rows9_dev, int* flags_dev);
-// ... B maps per launch (icp_batch_pmap_*, api.hip): descriptors filled on the host, one table copy, then the launches —
+// ... B maps per launch (icp_batch_pmap_*, batch.hip): descriptors filled on the host, one table copy, then the launches —
 // registration: pmap_launch_begin_batch (targets, states, z-buffers), per iteration pmap_launch_iteration_batch (projection
 // + association + partial rows) and launch_sum_solve_batch; update: pmap_launch_update_batch (insertions, model rebuild)
 size_t pmap_reg_desc_bytes();
@@ -835,6 +836,12 @@ int grid_sample_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, double vox
 // ---- profiling helpers (api.hip)
 int prof_begin(icp_ctx* ctx, int kind, int iter = -1);  // iter: index of the ICP iteration (search kernel)
 void prof_end(icp_ctx* ctx, int token);
+void prof_collect(icp_ctx* ctx);  // the pending event pairs -> the context's totals (their work has been waited for)
+
+// the developer statistics of option "search_stats": 16 path counters + 4 phase stamps per workgroup and iteration, then the
+// normal kernel's blocks
+static constexpr size_t DBG_ITER_BYTES = 64 + 24 * 1024 * 4 * sizeof(long long);
+static constexpr size_t DBG_BYTES = DBG_ITER_BYTES + 8192 * 4 * sizeof(long long);
 
 inline RegState* reg_state(icp_ctx* ctx) { return ctx->state.as<RegState>(); }
 
@@ -863,6 +870,46 @@ inline bool wants_eager_normals(const icp_ctx* ctx, int64_t n) {
 }
 
 }  // namespace icp
+
+// ---- host helpers of the C ABI's units that one of its other units calls (api.hip, register.hip, batch.hip, search_stats.hip)
+// iterations a chunked launch still holds back run against the map / configuration they were launched with: they go first
+#define ICP_HELD_FIRST(ctx)                                  \
+    do {                                                     \
+        const int _rc_held = continue_launch((ctx), -1);     \
+        if (_rc_held) return _rc_held;                       \
+    } while (0)
+// api.hip: the contexts of this process with a registration in flight, per device
+extern std::atomic<int> g_registering[64];
+void registering_enter(icp_ctx* ctx);
+void registering_leave(icp_ctx* ctx);
+// api.hip: staging, the registration state, the bodies of the map updates and the projective window
+int import_buffer(icp_ctx* ctx, const void* src, size_t n_bytes, int mem, icp::DeviceBuffer& stage, const void** dev_out);
+int stage_targets(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode);
+int ensure_state(icp_ctx* ctx);
+int prepare_targets_and_state(icp_ctx* ctx, int64_t n, const float* init_pose, bool keep_pose = false,
+                              icp::PackDesc* defer = nullptr);
+bool frame_in_flight(const icp_ctx* ctx);
+int map_update_impl(icp_ctx* ctx, const float rel_pose[16], const float* new_dev, const int* flags_dev, int64_t n,
+                    bool has_cloud, int64_t* inserted_out, int64_t known_count = -1);
+int map_update_body(icp_ctx* ctx, const float rel_pose[16], const float* new_dev, const int* flags_dev, int64_t n,
+                    bool has_cloud, int64_t* inserted_out, int64_t known_count, icp::GridBuildDesc* defer = nullptr);
+int map_update_finish(icp_ctx* ctx);
+int pmap_window_check(const icp_ctx* ctx, const float rel_pose[16], bool insert, const char** why);
+int pmap_free_slot(const icp_ctx* ctx);
+void pmap_window_step(icp_ctx* ctx, const float rel_pose[16], int slot);
+// register.hip: the two begins, the result hand-over and the iterations a chunked launch holds back
+bool fused_path(const icp_ctx* ctx);
+int register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16],
+                   bool from_last, icp::PackDesc* defer_pack = nullptr);
+int pmap_register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16],
+                        bool from_last, icp::PackDesc* defer_pack, bool pose_now);
+void result_fold_reset(icp_ctx* ctx);
+int result_fold_begin(icp_ctx* ctx, bool refresh);
+int result_hand_over(icp_ctx* ctx, int rc, int enqueued, int remaining, bool refresh = false,
+                     hipEvent_t shared_event = nullptr);
+int continue_launch(icp_ctx* ctx, int count);
+// search_stats.hip: the "search_stats" dump of a collected registration to stderr (nothing unless the option is on)
+void search_stats_report(icp_ctx* ctx, const icp::RegState& st);
 
 // Every entry point runs on the context's device and leaves the calling thread's current device as it found it (a
 // process may hold contexts on several GPUs, and torch shares the thread's current device with us).
