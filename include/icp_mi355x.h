@@ -421,6 +421,25 @@ int icp_knn_query(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int32_t k,
  * the fused iteration kernel keeps, and rows 0-2 of the pose that iteration ran with (pose_out, host memory, may be
  * NULL).  Valid right after icp_register / icp_register_end, before the map changes; ICP_ERR_INVALID_ARGUMENT otherwise. */
 int icp_last_neighbors(icp_ctx* ctx, int32_t* neighbor_index_out, float pose_out[12], int out_mem);
+/* Test support for the certificates of that cache (no reference counterpart): the entry of every target of the last
+ * registration as its last fused launch left it.  An entry is a candidate set S of up to three map points and a lower
+ * bound L on the distance from the target, at the pose of the iteration that searched it, to every map point NOT in S; a
+ * later iteration keeps it while sqrt(d2_winner) * 1.000001 < L - (|displacement| * 1.000001 + 1e-7) - margin.
+ *   members_out           [n,3] int32: ORIGINAL map indices, the stored neighbour first, -1: none
+ *   bound_out             [n] float32: L (0: the entry certifies nothing)
+ *   search_iteration_out  [n] int32: the iteration of the search, the 7-bit field resolved to the largest j <= last with
+ *                         j = field (mod 128); -1 for masked rows and empty entries (members -1, L 0)
+ *   records_out           [n,8] float32, only under option "hit_records" (ICP_ERR_INVALID_ARGUMENT otherwise): the two
+ *                         float4 of the row's hit record, (winner xyz, bound), (normal, bits(iteration of the bound; -1: none));
+ *                         a device pointer must be 16-byte aligned
+ *   pose_hist_out         HOST memory, [last + 1, 12] float32: rows 0-2 of the pose of every iteration 0 .. last
+ *   last_iteration_out    HOST memory: `last`, the iteration icp_last_neighbors reports (call with the other outputs NULL
+ *                         to size pose_hist_out)
+ * Every output may be NULL.  Valid and refused in the states of icp_last_neighbors (icp_last_error says which); reads the
+ * targets, the entries, the map points and the records, and stages through a buffer of its own: the cache, the normals and
+ * the registration state are left as they were. */
+int icp_last_cache_entries(icp_ctx* ctx, int32_t* members_out, float* bound_out, int32_t* search_iteration_out,
+                           float* records_out, float* pose_hist_out, int32_t* last_iteration_out, int out_mem);
 
 /* ---- projective local map: ProjectiveLocalMap (slam/odometry/local_map.py:91-240), the reference's "GPU" variant -----
  * compute_normal_map (slam/common/geometry.py:240-295): vertex map [3,H,W] -> normal map [3,H,W] (box-filter plane fit,

@@ -324,7 +324,7 @@ void icp_destroy(icp_ctx* ctx) {
                             &ctx->pm_n,       &ctx->pm_mv,      &ctx->pm_mn,      &ctx->pm_z,      &ctx->pm_tmp,
                             &ctx->vox_out,    &ctx->seed_orig,  &ctx->scan_desc,  &ctx->posebox,   &ctx->pose_hist_buf,
                             &ctx->hood,       &ctx->normals_carry, &ctx->tail_rows, &ctx->normals_tail, &ctx->nn_rec,
-                            &ctx->knn_in,     &ctx->knn_dist,   &ctx->knn_idx,
+                            &ctx->knn_in,     &ctx->knn_dist,   &ctx->knn_idx,    &ctx->cache_out,
                             &ctx->cell_list[0][0], &ctx->cell_list[0][1], &ctx->cell_list[1][0], &ctx->cell_list[1][1], &ctx->cell_counts};
     for (DeviceBuffer* b : bufs) b->release();
     for (auto& r : ctx->rslot) {
@@ -1103,6 +1103,46 @@ int icp_last_neighbors(icp_ctx* ctx, int32_t* neighbor_index_out, float pose_out
     if ((rc = export_finish(ctx, neighbor_index_out, idev, (size_t)n * 4, out_mem))) return rc;
     if (pose_out)
         ICP_HIP(ctx, hipMemcpyAsync(pose_out, ctx->pose_hist + (size_t)it * 12, 12 * sizeof(float), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ICP_OK;
+}
+
+int icp_last_cache_entries(icp_ctx* ctx, int32_t* members_out, float* bound_out, int32_t* search_iteration_out,
+                           float* records_out, float* pose_hist_out, int32_t* last_iteration_out, int out_mem) {
+    DeviceGuard device_guard(ctx);
+    if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    if (ctx->in_registration || ctx->result_pending())
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_last_cache_entries: registration in progress");
+    // (the states icp_last_neighbors reads in: the entries describe the targets of the last registration and the current grid)
+    if (!ctx->cache_fresh || ctx->cache_n <= 0 || ctx->cache_n != ctx->tgt_n || ctx->cache_gen != ctx->grid_gen || !ctx->grid_valid ||
+        ctx->iter_in_registration <= 0 || ctx->last_iterations <= 0 || !ctx->pose_hist)
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_last_cache_entries: no fused registration against the current map to read entries from");
+    const int last = (ctx->last_iterations < ctx->iter_in_registration ? ctx->last_iterations : ctx->iter_in_registration) - 1;
+    if (last >= ctx->hist_cap) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_last_cache_entries: pose history too short");
+    const size_t n = (size_t)ctx->tgt_n;
+    if (records_out && (!ctx->hit_records || !ctx->nn_rec.ptr || ctx->nn_rec.bytes < n * 32))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_last_cache_entries: no hit records (option \"hit_records\" is off)");
+    if (last_iteration_out) *last_iteration_out = last;
+    // one staging buffer of this entry point alone, carved: records (float4: 16-byte aligned at its head) | members | L | iteration
+    const size_t off_m = n * 32, off_b = n * 44, off_i = n * 48, total = n * 52;
+    char* stage = nullptr;
+    if (out_mem != ICP_MEM_DEVICE) {
+        ICP_HIP(ctx, ctx->cache_out.reserve(total));
+        stage = ctx->cache_out.as<char>();
+    }
+    int* mdev = !members_out ? nullptr : stage ? (int*)(stage + off_m) : (int*)members_out;
+    float* bdev = !bound_out ? nullptr : stage ? (float*)(stage + off_b) : bound_out;
+    int* idev = !search_iteration_out ? nullptr : stage ? (int*)(stage + off_i) : (int*)search_iteration_out;
+    float* rdev = !records_out ? nullptr : stage ? (float*)stage : records_out;
+    int rc;
+    if ((rc = launch_last_cache_entries(ctx, last, mdev, bdev, idev, rdev))) return rc;
+    if ((rc = export_finish(ctx, members_out, mdev, n * 12, out_mem))) return rc;
+    if ((rc = export_finish(ctx, bound_out, bdev, n * 4, out_mem))) return rc;
+    if ((rc = export_finish(ctx, search_iteration_out, idev, n * 4, out_mem))) return rc;
+    if ((rc = export_finish(ctx, records_out, rdev, n * 32, out_mem))) return rc;
+    if (pose_hist_out)
+        ICP_HIP(ctx, hipMemcpyAsync(pose_hist_out, ctx->pose_hist, (size_t)(last + 1) * 12 * sizeof(float), hipMemcpyDeviceToHost,
                                     ctx->stream));
     ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ICP_OK;

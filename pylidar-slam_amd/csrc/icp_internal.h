@@ -605,6 +605,7 @@ struct icp_ctx {
     icp::DeviceBuffer zbuf, stage_in, stage_out, stage_out2, flags, scan_a, scan_b, sort_tmp, keys_a, keys_b, vals_a,
         vals_b, counter;
     icp::DeviceBuffer knn_in, knn_dist, knn_idx;  // staging of icp_knn_query alone: a query leaves every other buffer as it was
+    icp::DeviceBuffer cache_out;  // staging of icp_last_cache_entries alone
     // ---- projective local map (row a19)
     icp::DeviceBuffer pm_v, pm_n, pm_mv, pm_mn, pm_z, pm_tmp;
     std::vector<int> pm_slots;                 // storage slot of every kept map, oldest first
@@ -701,6 +702,8 @@ int launch_normals_batch(icp_ctx* first, int kn, const NormalsBatchDesc* table_h
                          int count);
 int launch_gather_neighbors(icp_ctx* ctx, int64_t n, float* pts_out, float* nrm_out, int32_t* idx_out);
 int launch_last_neighbors(icp_ctx* ctx, int iteration, int* out_dev);  // NN cache -> matched map point per target (tests)
+// NN cache -> members, L and search iteration per target; `rec_dev`: the hit records too (tests)
+int launch_last_cache_entries(icp_ctx* ctx, int last, int* members_dev, float* bound_dev, int* iter_dev, float* rec_dev);
 // map-sharded normals: the owned share by original index (zeros elsewhere) / install the all-reduced array
 int launch_normals_owned(icp_ctx* ctx, int rank, int world, float* by_index_dev);
 int launch_normals_install(icp_ctx* ctx, const float* by_index_dev);

@@ -1394,7 +1394,7 @@ static_assert(BATCH_LEAD_SLOTS % 8 == 0 && BATCH_LEAD_SLOTS == ICP_BATCH_MAX_SEQ
 
 // cache entry .x = cell-sorted position of the neighbour | iteration of the search << 24 (-1: no neighbour); a position
 // needs 24 bits (maps of up to 16.7 M points use the cache), iterations wrap into 7 bits — harmlessly: an entry older
-// than CACHE_HIST launches is a miss
+// than CACHE_HIST launches is a miss, so the cache test resolves the field to the nearest iteration at or before its own
 // The square root of the cache tests: the hardware's v_sqrt_f32 (1 ulp) instead of the correctly rounded sqrtf() (which the
 // compiler expands to 14 instructions: scaling for denormals, two correction steps, a class test).  The tests are BOUNDS, not
 // results — a hit is certified when an upper bound of the winner's distance is below a lower bound of everybody else's — and
@@ -1787,7 +1787,10 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
                     }
                 }
                 if (!hit && c.x >= 0) {
-                    const int k = (int)((unsigned)c.x >> CACHE_ITER_SHIFT), age = iter_now - k;  // searched `age` launches ago
+                    // searched `age` launches ago, in iteration k (the 7-bit field resolved against this iteration: an entry
+                    // lives CACHE_HIST launches at the most, so its age is the difference modulo 128 — taken plainly, every
+                    // entry written from iteration 128 on looked 128 launches old and the cache never hit again)
+                    const int age = (iter_now - (int)((unsigned)c.x >> CACHE_ITER_SHIFT)) & 127, k = iter_now - age;
                     float dx = cq.x - px, dy = cq.y - py, dz = cq.z - pz;
                     float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
                     int hit_pos = c.x & CACHE_POS_MASK;
@@ -2307,7 +2310,7 @@ __device__ __forceinline__ void iterate_late_body(GridView g, IterInputs in, Reg
             if (!hit) {
                 const int4 c = in.nn_cache[qi];
                 if (c.x >= 0) {
-                    const int k = (int)((unsigned)c.x >> CACHE_ITER_SHIFT), age = iter_now - k;
+                    const int age = (iter_now - (int)((unsigned)c.x >> CACHE_ITER_SHIFT)) & 127, k = iter_now - age;  // (as in iterate_body)
                     int hit_pos = c.x & CACHE_POS_MASK;
                     float4 wq = g.pts[hit_pos];
                     float4 cq2 = wq, cq3 = wq;
@@ -4394,6 +4397,54 @@ int launch_last_neighbors(icp_ctx* ctx, int iteration, int* out_dev) {
     hipLaunchKernelGGL(k_last_neighbors, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->tgt4.as<float4>(),
                        ctx->nn_cache.as<int4>(), ctx->sorted_pts.as<float4>(), ctx->pose_hist + (size_t)iteration * 12, n,
                        ctx->tgt_mode, (int)ctx->map_m, out_dev);
+    ICP_HIP(ctx, hipGetLastError());
+    return ICP_OK;
+}
+
+// The NN-cache entry of every target as the last fused launch left it (test support, icp_last_cache_entries): the members
+// of the candidate set as ORIGINAL map indices (the stored neighbour first, -1: none), L, and the iteration of the search
+// resolved to a full number — the largest j <= last with j = the 7-bit field (mod 128); masked rows and empty entries: -1.
+// `rec_out` (hit records on): the two float4 of the row's record, (0, 0, 0, 0 | 0, 0, 0, bits(-1)) for such rows.
+// A plain gather: reads the targets, the entries, the points and the records; writes its outputs only.
+__global__ void k_last_cache_entries(const float4* __restrict__ tgt, const int4* __restrict__ cache,
+                                     const float4* __restrict__ pts, const float4* __restrict__ rec, int n, int mode, int m,
+                                     int last, int* __restrict__ members, float* __restrict__ bound, int* __restrict__ iter_out,
+                                     float4* __restrict__ rec_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 t4 = tgt[i];
+    const int4 c = cache[i];
+    int m0 = -1, m1 = -1, m2 = -1, j = -1;
+    float L = 0.f;
+    const bool live = target_valid(t4.x, t4.y, t4.z, mode) && c.x >= 0;
+    if (live) {
+        const int p0 = c.x & CACHE_POS_MASK;
+        if (p0 < m) m0 = __float_as_int(pts[p0].w);
+        if (c.z >= 0 && c.z < m) m1 = __float_as_int(pts[c.z].w);
+        if (c.w >= 0 && c.w < m) m2 = __float_as_int(pts[c.w].w);
+        L = __int_as_float(c.y);
+        j = last - ((last - (int)((unsigned)c.x >> CACHE_ITER_SHIFT)) & 127);
+        if (j < 0) j = -1;
+    }
+    if (members) {
+        members[3 * (size_t)i] = m0;
+        members[3 * (size_t)i + 1] = m1;
+        members[3 * (size_t)i + 2] = m2;
+    }
+    if (bound) bound[i] = L;
+    if (iter_out) iter_out[i] = j;
+    if (rec_out) {
+        rec_out[2 * (size_t)i] = live ? rec[2 * (size_t)i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        rec_out[2 * (size_t)i + 1] = live ? rec[2 * (size_t)i + 1] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+    }
+}
+
+int launch_last_cache_entries(icp_ctx* ctx, int last, int* members_dev, float* bound_dev, int* iter_dev, float* rec_dev) {
+    const int n = (int)ctx->tgt_n;
+    if (n <= 0) return ICP_OK;
+    hipLaunchKernelGGL(k_last_cache_entries, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->tgt4.as<float4>(),
+                       ctx->nn_cache.as<int4>(), ctx->sorted_pts.as<float4>(), ctx->nn_rec.as<float4>(), n, ctx->tgt_mode,
+                       (int)ctx->map_m, last, members_dev, bound_dev, iter_dev, (float4*)rec_dev);
     ICP_HIP(ctx, hipGetLastError());
     return ICP_OK;
 }

@@ -154,6 +154,7 @@ EXPORTED_SYMBOLS = {
     "icp_nearest_neighbor_search": (_INT, [_P, _P, _I64, _INT, _P, _P, _P, _INT]),
     "icp_knn_query": (_INT, [_P, _P, _I64, _INT, C.c_int32, C.c_float, C.c_int32, _P, _P, _INT]),
     "icp_last_neighbors": (_INT, [_P, _P, _P, _INT]),
+    "icp_last_cache_entries": (_INT, [_P, _P, _P, _P, _P, _P, _P, _INT]),
     "icp_compute_normal_map": (_INT, [_P, _P, _INT, _INT, _P, _INT]),
     "icp_compute_neighbors": (_INT, [_P, _P, _P, _P, _INT, _INT, _INT, _P, _P, _INT]),
     "icp_pmap_init": (_INT, [_P]),

@@ -567,6 +567,25 @@ class IcpContext:
         self._check(self._lib.icp_last_neighbors(self._h, ix.ctypes.data, pose.ctypes.data, MEM_HOST))
         return ix, pose.reshape(3, 4)
 
+    def last_cache_entries(self, n: int, records: bool = False):
+        """The NN-cache entry of every target of the last registration (test support: `icp_last_cache_entries`): a dict of
+        `members` [n, 3] original map indices (the stored neighbour first, -1: none), `bound` [n] (L), `iteration` [n] (of
+        the search, -1: no entry), `pose_hist` [last + 1, 3, 4], `last`, and with `records` the raw `records` [n, 8]."""
+        last = C.c_int32(-1)
+        self._check(self._lib.icp_last_cache_entries(self._h, None, None, None, None, None, C.byref(last), MEM_HOST))
+        n = int(n)
+        members, bound = np.empty((n, 3), np.int32), np.empty(n, np.float32)
+        iteration, hist = np.empty(n, np.int32), np.empty((last.value + 1, 12), np.float32)
+        rec = np.empty((n, 8), np.float32) if records else None
+        self._check(self._lib.icp_last_cache_entries(self._h, members.ctypes.data, bound.ctypes.data, iteration.ctypes.data,
+                                                     rec.ctypes.data if records else None, hist.ctypes.data, C.byref(last),
+                                                     MEM_HOST))
+        out = {"members": members, "bound": bound, "iteration": iteration, "pose_hist": hist.reshape(-1, 3, 4),
+               "last": int(last.value)}
+        if records:
+            out["records"] = rec
+        return out
+
     # ---- projective local map (SURVEY §8 row a19) --------------------------------------------------------------------
     def _planar(self, vmap: Array):
         """[3,H,W] float32 contiguous -> (pointer, mem, keep-alive)."""
