@@ -228,6 +228,15 @@ int icp_synchronize(icp_ctx* ctx);
  *   "insert_by_cell" 0 | 1 (1)      behind a map update the points claim their cells of the new grid in the cell order of the
  *                                   previous grid (a rigid step leaves the points of an old cell in one or two new ones: the lanes
  *                                   of a wave share their claims) instead of in insertion order
+ *   "clear_ahead" 0 | 1 (1)         a second hash table (+ 32 B per table slot: 4 MB at the headline sizes, 32 MB for a million
+ *                                   map points, allocated at the first launched registration): extra workgroups of the last
+ *                                   solving launch of an enqueued registration empty it beside the one workgroup that solves;
+ *                                   the next grid build of that size inserts into it without a clearing pass and the tables
+ *                                   change places.  A build that finds no clean spare of its size (no registration in front
+ *                                   of it, a table that grew) clears in its own first launch as before; same bits
+ *   "move_on_insert" 0 | 1 (1)      a build into a clean table has no clearing launch: the re-expression of the kept points, the
+ *                                   carried normals, the NN cache -> seed conversion and two counter resets ride in the
+ *                                   insertion launch (insert, scan, scatter: three launches per pose-only update); same bits
  *   "normals_list" 0 | 1 (0)        the stragglers of the eager kNN normals — the ~0.3 % of the map points whose k-th neighbour
  *                                   the pair pass does not certify — go to a list and a launch of their own right behind the
  *                                   estimating one: sixteen lanes per point, exact keys, DPP merges, ring 2 by hashed probes

@@ -312,7 +312,7 @@ void icp_destroy(icp_ctx* ctx) {
     (void)hipDeviceSynchronize();
     frame_loop_release(ctx);
     pmap_frame_loop_release(ctx);
-    DeviceBuffer* bufs[] = {&ctx->map_xyz[0], &ctx->map_xyz[1], &ctx->table,   &ctx->sorted_pts, &ctx->normals,
+    DeviceBuffer* bufs[] = {&ctx->map_xyz[0], &ctx->map_xyz[1], &ctx->table,   &ctx->table_spare, &ctx->sorted_pts, &ctx->normals,
                             &ctx->nflag,      &ctx->slot_of,    &ctx->rank_of, &ctx->scan_tmp,   &ctx->worklist,
                             &ctx->targets,    &ctx->nn_pos,     &ctx->partials, &ctx->state,
                             &ctx->neq_own,    &ctx->zbuf,    &ctx->stage_in,   &ctx->stage_out,
@@ -401,6 +401,8 @@ int icp_set_option(icp_ctx* ctx, const char* name, double value) {
     else if (k == "far_max") ctx->far_max = iv < 0 ? 0 : (iv > 512 ? 512 : (int)iv);
     else if (k == "insert_by_cell") ctx->insert_by_cell = iv != 0 ? 1 : 0;
     else if (k == "cell_lists") ctx->cell_lists = iv != 0 ? 1 : 0;
+    else if (k == "clear_ahead") ctx->clear_ahead = iv != 0 ? 1 : 0;
+    else if (k == "move_on_insert") ctx->move_on_insert = iv != 0 ? 1 : 0;
     else if (k == "normals_tail_stream") ctx->normals_tail_stream = iv != 0 ? 1 : 0;
     else if (k == "normals_list") ctx->normals_list = iv != 0 ? 1 : 0;
     else if (k == "ball_lanes") ctx->ball_lanes = iv >= 8 ? 8 : (iv >= 4 ? 4 : (iv >= 2 ? 2 : 1));

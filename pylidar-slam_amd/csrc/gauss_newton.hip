@@ -329,7 +329,20 @@ __global__ __launch_bounds__(1024) void k_sum_solve(const double* __restrict__ p
                                                     float* __restrict__ dx_hist, int hist_cap,
                                                     unsigned long long* __restrict__ box, unsigned gen,
                                                     const unsigned* __restrict__ result_src, unsigned* __restrict__ result_dst,
-                                                    int result_words) {
+                                                    int result_words, GridEntry* __restrict__ spare,
+                                                    unsigned spare_entries) {
+    // "clear_ahead": workgroups 1 .. gridDim.x - 1 of the LAST solving launch of an enqueued registration empty the spare
+    // hash table (the next grid build inserts into it without a clearing pass) while workgroup 0 sums and solves — the chip
+    // is idle beside it.  They wait for nothing and nothing of this launch waits for them
+    if (blockIdx.x != 0) {  // block-uniform
+        GridEntry e;
+        e.key = GRID_EMPTY;
+        e.start = 0;
+        e.count = 0;
+        const unsigned stride = (gridDim.x - 1) * blockDim.x;
+        for (unsigned i = (blockIdx.x - 1) * blockDim.x + threadIdx.x; i < spare_entries; i += stride) spare[i] = e;
+        return;
+    }
     sum_solve_body(partials, nblocks, quad, st, ap, neq, loss_hist, dx_hist, hist_cap, box, gen, result_src, result_dst,
                    result_words);
 }
@@ -497,6 +510,28 @@ int launch_sum_solve(icp_ctx* ctx, int blocks, int quad, const double* partials,
     // the last solving launch of an enqueued registration delivers the result block itself (api.hip::enqueue_result_copy)
     unsigned* fold = (last && !ctx->exchange_on) ? reinterpret_cast<unsigned*>(ctx->result_fold_to) : nullptr;
     if (fold) ctx->result_folded = true;
+    // the spare table emptied beside the final solve (grid_tables_plan.h): allocated at the first such launch
+    GridEntry* spare = nullptr;
+    unsigned spare_entries = 0, clear_blocks = 0;
+    if (last && ctx->grid_valid) {
+        GridTablesMode mode;
+        mode.clear_ahead = ctx->clear_ahead != 0;
+        mode.cell_lists = ctx->cell_lists != 0;
+        mode.excluded = ctx->exchange_on || ctx->overlap_map_update || ctx->prof.enabled || ctx->search_stats;
+        bool realloc = false;
+        if (solve_clears_spare(ctx->tables, ctx->table_size, mode, &realloc)) {
+            const size_t need = (size_t)2 * ctx->table_size * sizeof(GridEntry);
+            const hipError_t e = ctx->table_spare.reserve(need);  // (nothing to do unless `realloc`, and not always then)
+            if (e != hipSuccess) {
+                spare_lost(ctx->tables);
+                ICP_HIP(ctx, e);
+            }
+            spare = ctx->table_spare.as<GridEntry>();
+            spare_entries = 2u * ctx->table_size;
+            clear_blocks = (spare_entries + 1023u) / 1024u;
+            if (clear_blocks > 1023u) clear_blocks = 1023u;  // (four waves of workgroups on 256 CUs at most: grid-stride beyond)
+        }
+    }
     if (ctx->exchange_on) {
         ExchangeView x = ctx->xview;
         x.timeout_ticks = (long long)(ctx->exchange_timeout_ms * 1.0e5);  // 100 MHz
@@ -504,12 +539,13 @@ int launch_sum_solve(icp_ctx* ctx, int blocks, int quad, const double* partials,
                            blocks, quad, reg_state(ctx), make_align_params(ctx), ctx->neq, ctx->loss_hist,
                            ctx->dx_hist, ctx->hist_cap, x);
     } else {
-        hipLaunchKernelGGL(k_sum_solve, dim3(1), dim3(1024), 0, ctx->stream, partials, blocks, quad,
+        hipLaunchKernelGGL(k_sum_solve, dim3(1 + clear_blocks), dim3(1024), 0, ctx->stream, partials, blocks, quad,
                            reg_state(ctx), make_align_params(ctx), ctx->neq, ctx->loss_hist, ctx->dx_hist,
                            ctx->hist_cap, publish ? pose_box(ctx) : (unsigned long long*)nullptr,
                            publish ? next_box_generation(ctx) : 0u, ctx->state.as<unsigned>(), fold,
-                           fold ? (int)(ctx->result_fold_bytes / 4) : 0);
+                           fold ? (int)(ctx->result_fold_bytes / 4) : 0, spare, spare_entries);
     }
+    if (spare && hipPeekAtLastError() != hipSuccess) spare_lost(ctx->tables);
     ICP_HIP(ctx, hipGetLastError());
     return ICP_OK;
 }

@@ -314,6 +314,36 @@ int compact_valid_rows_batch(icp_ctx* const* ctxs, int count, const float* const
 // alternation (`lists.prev` was written by the previous build).  The ORDER of the cells in the cell-sorted arrays becomes the
 // order of the claims — as immaterial as the order of the points inside a cell already was: every consumer breaks ties on the
 // original index, every sum over a neighbourhood is order-independent.
+// (the per-point parts of the first launch of a build: shared by grid_clear_body and — "move_on_insert" — grid_insert2_body)
+// NN-cache entry i -> the original index its neighbour has after this update (-1: none)
+__device__ __forceinline__ void seed_from_cache(const int4* __restrict__ nn_cache, const float4* __restrict__ old_pts, int old_m,
+                                                int evicted, int* __restrict__ seed, int i) {
+    const int x = nn_cache[i].x, pos = x & 0xffffff;  // (.x = position | iteration << 24, search.hip)
+    int o = -1;
+    if (x >= 0 && pos < old_m) o = __float_as_int(old_pts[pos].w) - evicted;
+    seed[i] = o;
+}
+
+// the normal at cell-sorted position i of the OLD grid, rotated by T and filed by original index
+__device__ __forceinline__ void carry_normal(const float* T, const float4* __restrict__ old_pts,
+                                             const float4* __restrict__ old_normals, const int* __restrict__ old_nflag,
+                                             int carry_m, float4* __restrict__ carry, int i) {
+    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 p = old_pts[i];
+    if (old_nflag[i] == 1) {
+        const float4 nv = old_normals[i];
+        const float x = T[0] * nv.x + T[1] * nv.y + T[2] * nv.z, y = T[4] * nv.x + T[5] * nv.y + T[6] * nv.z,
+                    z = T[8] * nv.x + T[9] * nv.y + T[10] * nv.z;
+        // (re-normalised only once rounding has moved the length off 1 by more than an ulp or two: a rotation by the
+        // identity — the update behind a registration that failed — leaves every bit where it was)
+        const float n2 = x * x + y * y + z * z;
+        const float sc = fabsf(n2 - 1.f) > 4e-7f ? rsqrtf(n2) : 1.f;
+        if (n2 > 0.f && sc < INFINITY) out = make_float4(x * sc, y * sc, z * sc, 1.f);  // (a zero normal stays unestimated)
+    }
+    const int o = __float_as_int(p.w);
+    if (o >= 0 && o < carry_m) carry[o] = out;
+}
+
 __device__ __forceinline__ void grid_clear_body(GridEntry* __restrict__ table, unsigned int size, const int4* __restrict__ nn_cache,
                              const float4* __restrict__ old_pts, int seed_n, int old_m, int evicted,
                              int* __restrict__ seed, const MapMoveJob& move, int* __restrict__ scan_ticket,
@@ -342,31 +372,12 @@ __device__ __forceinline__ void grid_clear_body(GridEntry* __restrict__ table, u
             table[i] = e;
         }
     }
-    if ((int)i < seed_n) {
-        const int x = nn_cache[i].x, pos = x & 0xffffff;  // (.x = position | iteration << 24, search.hip)
-        int o = -1;
-        if (x >= 0 && pos < old_m) o = __float_as_int(old_pts[pos].w) - evicted;
-        seed[i] = o;
-    }
+    if ((int)i < seed_n) seed_from_cache(nn_cache, old_pts, old_m, evicted, seed, (int)i);
     if (moves) {
         __syncthreads();
         if ((long long)i < move.m) move_point(T, move.in, (long long)i, move.out);
-        if ((int)i < carry_m) {  // (carry_m == move.m: this block has T)
-            float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 p = old_pts[i];
-            if (old_nflag[i] == 1) {
-                const float4 nv = old_normals[i];
-                const float x = T[0] * nv.x + T[1] * nv.y + T[2] * nv.z, y = T[4] * nv.x + T[5] * nv.y + T[6] * nv.z,
-                            z = T[8] * nv.x + T[9] * nv.y + T[10] * nv.z;
-                // (re-normalised only once rounding has moved the length off 1 by more than an ulp or two: a rotation by the
-                // identity — the update behind a registration that failed — leaves every bit where it was)
-                const float n2 = x * x + y * y + z * z;
-                const float sc = fabsf(n2 - 1.f) > 4e-7f ? rsqrtf(n2) : 1.f;
-                if (n2 > 0.f && sc < INFINITY) out = make_float4(x * sc, y * sc, z * sc, 1.f);  // (a zero normal stays unestimated)
-            }
-            const int o = __float_as_int(p.w);
-            if (o >= 0 && o < carry_m) carry[o] = out;
-        }
+        // (carry_m == move.m: this block has T)
+        if ((int)i < carry_m) carry_normal(T, old_pts, old_normals, old_nflag, carry_m, carry, (int)i);
     }
 }
 
@@ -466,11 +477,46 @@ __device__ inline void wave_group_by_key(unsigned long long key, bool active, in
 // the lanes of a wave share a handful of keys again — in insertion order a map merged from many grid-sampled clouds has 64
 // different cells per wave (64 trips of the grouping loop, 64 claims, 64 counter updates: 16.9 us at C2, 24 us at 181 695
 // points).  Which thread claims a point does not matter: ranks inside a cell come from atomics either way.
+// "move_on_insert": what the clearing launch carried besides the table stores, for a build whose table is clean already
+// (the spare a solving launch emptied: "clear_ahead") — this launch visits the same points right behind it.  Every workgroup
+// prepares the move once; the thread that claims point i < move.m forms it from move.in, stores it to move.out (= `xyz`, the
+// array the scatter reads) and hashes the value it has just formed: the same arithmetic, hence the same floats and keys.
+// Thread t (a cell-sorted position of the OLD grid) carries normal t and converts NN-cache entry t; thread 0 resets the two
+// counters later launches of the build draw from
+struct InsertRide {
+    MapMoveJob move;
+    const int4* nn_cache = nullptr;
+    const float4* old_pts = nullptr;
+    int seed_n = 0, seed_m = 0, seed_evicted = 0;
+    int* seed = nullptr;
+    int* scan_ticket = nullptr;
+    unsigned long long* hood_used = nullptr;
+    const float4* old_normals = nullptr;
+    const int* old_nflag = nullptr;
+    int carry_m = 0;
+    float4* carry = nullptr;
+};
+
 __device__ __forceinline__ void grid_insert2_body(const float* __restrict__ xyz, int m, float inv_h, float inv_hc,
                                GridEntry* __restrict__ table, unsigned int tsize, int* __restrict__ slot_of,
                                int* __restrict__ rank_of, int* __restrict__ cslot_of, int* __restrict__ crank_of,
                                const float4* __restrict__ old_pts, int old_m, int evicted, int kept,
-                               int* __restrict__ visit, const CellLists& lists, const unsigned bx) {
+                               int* __restrict__ visit, const CellLists& lists, const unsigned bx,
+                               const InsertRide* ride = nullptr) {
+    __shared__ float T[16];
+    const bool moves = ride && ride->move.m > 0;  // kernel-uniform
+    if (ride) {
+        if (bx == 0 && threadIdx.x == 0) {
+            *ride->scan_ticket = 0;                     // the tile numbers of this build's k_grid_scan
+            if (ride->hood_used) *ride->hood_used = 0;  // the list space k_hood_build hands out
+        }
+        if (moves && threadIdx.x == 0) map_move_prepare(ride->move, T);
+        if (moves) __syncthreads();
+        const int s = bx * blockDim.x + threadIdx.x;
+        if (s < ride->seed_n) seed_from_cache(ride->nn_cache, ride->old_pts, ride->seed_m, ride->seed_evicted, ride->seed, s);
+        if (moves && s < ride->carry_m)
+            carry_normal(T, ride->old_pts, ride->old_normals, ride->old_nflag, ride->carry_m, ride->carry, s);
+    }
     // (with `old_pts` the four outputs are indexed by THREAD and visit[thread] names the point, -1: none — the scatter walks
     // the same order, so that its stores by new position are clustered as well)
     const int t = bx * blockDim.x + threadIdx.x;
@@ -486,7 +532,9 @@ __device__ __forceinline__ void grid_insert2_body(const float* __restrict__ xyz,
         }
     }
     float x = 0.f, y = 0.f, z = 0.f;
-    if (active) {
+    if (active && moves && (long long)i < ride->move.m) {
+        move_point(T, ride->move.in, (long long)i, ride->move.out, &x, &y, &z);
+    } else if (active) {
         x = xyz[3 * i + 0];
         y = xyz[3 * i + 1];
         z = xyz[3 * i + 2];
@@ -549,6 +597,16 @@ __global__ void k_grid_insert2(const float* __restrict__ xyz, int m, float inv_h
                                int* __restrict__ visit, CellLists lists) {
     grid_insert2_body(xyz, m, inv_h, inv_hc, table, tsize, slot_of, rank_of, cslot_of, crank_of, old_pts, old_m, evicted, kept,
                       visit, lists, blockIdx.x);
+}
+
+// ... with the clearing launch's per-point work riding along ("move_on_insert"; never on cell lists)
+__global__ void k_grid_insert2_ride(const float* __restrict__ xyz, int m, float inv_h, float inv_hc,
+                                    GridEntry* __restrict__ table, unsigned int tsize, int* __restrict__ slot_of,
+                                    int* __restrict__ rank_of, int* __restrict__ cslot_of, int* __restrict__ crank_of,
+                                    const float4* __restrict__ old_pts, int old_m, int evicted, int kept,
+                                    int* __restrict__ visit, InsertRide ride) {
+    grid_insert2_body(xyz, m, inv_h, inv_hc, table, tsize, slot_of, rank_of, cslot_of, crank_of, old_pts, old_m, evicted, kept,
+                      visit, CellLists(), blockIdx.x, &ride);
 }
 
 // The starts of the cells from their counts, over the build's CELL LISTS: workgroup 0 the fine level, workgroup 1 the coarse
@@ -651,7 +709,7 @@ __device__ inline unsigned long long block_exclusive_scan_u64(unsigned long long
 // fine cells; tag = generation of this build << 2 | state (1: sum of the tile, 2: inclusive prefix).  Each word is written
 // and read by ONE relaxed agent-scope atomic, so no fence orders them: a reader takes a descriptor only when both tags
 // agree.  Stale descriptors of earlier builds carry another generation (the descriptors are zeroed when the generation
-// counter wraps).  A workgroup takes its tile number from a ticket counter (reset by k_grid_clear), so it only ever waits
+// counter wraps).  A workgroup takes its tile number from a ticket counter (reset by the build's first launch), so it only ever waits
 // for tiles whose workgroups are already running, whatever order the hardware dispatches blockIdx in.
 // ---------------------------------------------------------------------------------------------------------------------
 static constexpr unsigned SCAN_STATE_SUM = 1, SCAN_STATE_PREFIX = 2;
@@ -1018,6 +1076,19 @@ int build_grid(icp_ctx* ctx, GridBuildDesc* defer) {
     if (ctx->order_job && ctx->insert_by_cell && ctx->order_old_m + (m - ctx->order_kept) > claim_n)
         claim_n = ctx->order_old_m + (m - ctx->order_kept);
     const unsigned int tsize = next_pow2((unsigned int)(m + m / 4));
+    // which of the two tables this build fills, and whether its first launch has to empty it (grid_tables_plan.h): the spare a
+    // solving launch has emptied becomes the current table; otherwise in place, cleared here, as ever
+    GridTablesMode tables_mode;
+    tables_mode.clear_ahead = ctx->clear_ahead != 0;
+    tables_mode.deferred = defer != nullptr;
+    tables_mode.cell_lists = ctx->cell_lists != 0;
+    tables_mode.excluded = ctx->exchange_on || ctx->overlap_map_update || ctx->prof.enabled || ctx->search_stats;
+    const GridBuildTarget target = grid_build_target(ctx->tables, tsize, ctx->table.ptr ? ctx->table_size : 0u, tables_mode);
+    if (target.use_spare) {
+        const DeviceBuffer was_current = ctx->table;
+        ctx->table = ctx->table_spare;
+        ctx->table_spare = was_current;
+    }
     ICP_HIP(ctx, ctx->table.reserve((size_t)2 * tsize * sizeof(GridEntry)));  // fine level, then the coarse level
     ICP_HIP(ctx, ctx->csorted.reserve((size_t)m * sizeof(float4)));
     ICP_HIP(ctx, ctx->cslot_of.reserve((size_t)claim_n * sizeof(int)));
@@ -1146,6 +1217,7 @@ int build_grid(icp_ctx* ctx, GridBuildDesc* defer) {
         ctx->seed_job_n = 0;
         // threads of the clearing launch: one per table slot — or, with the previous build's cell lists, one per entry of those
         long long span = prev_cells_bound >= 0 ? (prev_cells_bound > 1 ? prev_cells_bound : 1) : n2;
+        if (!target.must_clear) span = 1;  // (a clean table: the per-point work only)
         if (seed_n > span) span = seed_n;
         const MapMoveJob move = ctx->move_job;  // the kept points re-expressed in the new frame (map update)
         ctx->move_job = MapMoveJob();
@@ -1218,12 +1290,35 @@ int build_grid(icp_ctx* ctx, GridBuildDesc* defer) {
         *defer = d;
         return ICP_OK;
     }
-    hipLaunchKernelGGL(k_grid_clear, dim3(d.clear_blocks), dim3(256), 0, ctx->stream, d.table, d.n2, d.nn_cache, d.old_pts,
-                       d.seed_n, d.seed_m, d.seed_evicted, d.seed, d.move, d.scan_ticket, d.hood_used, d.old_normals,
-                       d.old_nflag, d.carry_m, d.carry, d.lists);
-    hipLaunchKernelGGL(k_grid_insert2, dim3(d.visit_blocks), dim3(256), 0, ctx->stream, d.xyz, d.m, d.inv_h, d.inv_hc, d.table,
-                       d.tsize, d.slot_of, d.rank_of, d.cslot_of, d.crank_of, d.order_pts, d.order_old_m, d.order_evicted,
-                       d.order_kept, d.visit, d.lists);
+    if (!target.must_clear && ctx->move_on_insert) {  // insert -> scan -> scatter
+        InsertRide ride;
+        ride.move = d.move;
+        ride.nn_cache = d.nn_cache;
+        ride.old_pts = d.old_pts;
+        ride.seed_n = d.seed_n;
+        ride.seed_m = d.seed_m;
+        ride.seed_evicted = d.seed_evicted;
+        ride.seed = d.seed;
+        ride.scan_ticket = d.scan_ticket;
+        ride.hood_used = d.hood_used;
+        ride.old_normals = d.old_normals;
+        ride.old_nflag = d.old_nflag;
+        ride.carry_m = d.carry_m;
+        ride.carry = d.carry;
+        unsigned blocks = d.visit_blocks;
+        if ((unsigned)((d.seed_n + 255) / 256) > blocks) blocks = (unsigned)((d.seed_n + 255) / 256);
+        if ((unsigned)((d.move.m + 255) / 256) > blocks) blocks = (unsigned)((d.move.m + 255) / 256);
+        hipLaunchKernelGGL(k_grid_insert2_ride, dim3(blocks), dim3(256), 0, ctx->stream, d.xyz, d.m, d.inv_h, d.inv_hc, d.table,
+                           d.tsize, d.slot_of, d.rank_of, d.cslot_of, d.crank_of, d.order_pts, d.order_old_m, d.order_evicted,
+                           d.order_kept, d.visit, ride);
+    } else {
+        hipLaunchKernelGGL(k_grid_clear, dim3(d.clear_blocks), dim3(256), 0, ctx->stream, d.table, target.must_clear ? d.n2 : 0u, d.nn_cache,
+                           d.old_pts, d.seed_n, d.seed_m, d.seed_evicted, d.seed, d.move, d.scan_ticket, d.hood_used,
+                           d.old_normals, d.old_nflag, d.carry_m, d.carry, d.lists);
+        hipLaunchKernelGGL(k_grid_insert2, dim3(d.visit_blocks), dim3(256), 0, ctx->stream, d.xyz, d.m, d.inv_h, d.inv_hc,
+                           d.table, d.tsize, d.slot_of, d.rank_of, d.cslot_of, d.crank_of, d.order_pts, d.order_old_m,
+                           d.order_evicted, d.order_kept, d.visit, d.lists);
+    }
     if (d.lists.counts)
         hipLaunchKernelGGL(k_cells_scan, dim3(2), dim3(CS_THREADS), 0, ctx->stream, d.table, d.lists, d.ncells);
     else

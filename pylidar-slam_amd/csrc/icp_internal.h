@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "grid_tables_plan.h"
 #include "icp_mi355x.h"
 
 namespace icp {
@@ -363,8 +364,17 @@ struct icp_ctx {
     int map_cur = 0;                   // which of map_xyz[2] is current
     icp::DeviceBuffer map_xyz[2];      // [M,3] float, insertion order
     // ---- hash grid
-    icp::DeviceBuffer table;           // GridEntry[T]
+    icp::DeviceBuffer table;           // GridEntry[2 T]: the CURRENT table (fine level, then the coarse level)
     unsigned int table_size = 0;
+    // "clear_ahead": a second table of the same size, emptied by extra workgroups of the last solving launch of an enqueued
+    // registration (the chip is idle beside that one workgroup); the next grid build inserts into it without a clearing pass
+    // and the two buffers change places (grid_tables_plan.h holds the rule, hash_grid.hip and gauss_newton.hip apply it)
+    icp::DeviceBuffer table_spare;
+    icp::GridTablesState tables;
+    int clear_ahead = 1;
+    // "move_on_insert": a build whose table is clean already has no clearing launch: the re-expression of the kept points,
+    // the carried normals, the NN cache -> seed conversion and the counter resets ride in the insertion launch
+    int move_on_insert = 1;
     icp::DeviceBuffer sorted_pts;      // float4[M]
     icp::DeviceBuffer normals;         // float4[M] (by cell-sorted position)
     icp::DeviceBuffer nflag;           // int[M]: 0 none, 2 queued, 1 ready
