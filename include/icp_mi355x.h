@@ -1102,6 +1102,101 @@ int icp_elevation_get(icp_elevation* img, uint8_t* rgb_out, float* theta_out, fl
 /* the counters of the last build (synchronises): what slam/common/registration.py:196-241 kept (:205), dropped and painted */
 int icp_elevation_stats(icp_elevation* img, icp_elevation_counters* out);
 
+/* ---- cloud-to-cloud refinement: point-to-point ICP of one cloud against another ------------------------------------------
+ * ElevationImageLoopClosure._compute_transform of the reference (slam/loop_closure.py:210-225, called at :237-243 on the
+ * `points_3D` of a candidate image and of the current one): Open3D's registration_icp with TransformationEstimationPointToPoint,
+ * a distance threshold of 1.0 m, at most 30 iterations, relative_fitness = relative_rmse = 1e-6.  A refiner belongs to the
+ * context it was created on, like an aggregated map or an elevation image: its work goes on that context's stream, its buffers
+ * and its search grid are its own (every call is legal between icp_register_launch and icp_register_end and inside a frame
+ * call, and leaves the map, the grid, the normals, the nearest-neighbour cache and the registration state untouched), it is
+ * destroyed before the context is.  Several refiners may live on one context.
+ *   rows        float32 [n,3].  A target row with a NaN or infinite coordinate is never matched; a source row with one has no
+ *               correspondence and counts in the fitness denominator.  Under ICP_REFINE_DROP_ZERO_ROWS a row of either cloud
+ *               whose float32 (x*x + y*y) + z*z is not > 0 is left out altogether — not matched, not counted, in no sum: the
+ *               reference's `norm > 0` filter (:238-241), so that an [H,W,3] points_3D image can be passed as it is.
+ *               Correspondences always name ORIGINAL target rows.
+ *   transform   T float64 [4,4], source into target, starts as `init`.  A moved point is p'_a = ((T_a0 x + T_a1 y) + T_a2 z) +
+ *               T_a3 on the float32 coordinates converted to float64, always from the ORIGINAL row, without contraction.
+ *   search      over the target rows q: d2 = (dx dx + dy dy) + dz dz in float64, dx = p'_x - (double)q_x; q is a candidate iff
+ *               d2 < max_distance * max_distance (the float64 product; strict, as the bound of icp_knn_query); the winner is the
+ *               smallest (d2, target row): exact ties go to the lower row.  No result depends on cell_size.
+ *   evaluation  fitness = correspondences / counted source rows, inlier_rmse = sqrt(sum d2 / correspondences); both 0 without
+ *               correspondences.
+ *   step        Umeyama without scaling over the correspondences: means mu_p, mu_q, H = sum (q - mu_q)(p' - mu_p)^T / n,
+ *               H = U S V^T, R = U diag(1, 1, sign(det U det V)) V^T, t = mu_q - R mu_p; the identity without a correspondence;
+ *               T <- update T as a plain float64 4 x 4 product.  R is computed as the unit quaternion of the greatest eigenvalue
+ *               of Horn's 4 x 4 matrix of H (Jacobi rotations): the same rotation where it is unique, a proper rotation always.
+ *   loop        evaluate at init; then up to max_iteration times: step, evaluate, stop when |fitness - previous| <
+ *               relative_fitness and |inlier_rmse - previous| < relative_rmse.  max_iteration = 0 evaluates only.
+ *   history     for every evaluation the T it ran with and 17 figures: count, sum d2, mu_p [3], mu_q [3], H [9] row-major.
+ *   deviations  Open3D moves its copy of the source incrementally by every update (the rounding of 30 moves piles up in the
+ *               points); here every iteration moves the original row by the accumulated T.  Open3D's kd-tree leaves ties to its
+ *               traversal order; here the lower row wins.  Open3D's Eigen SVD and the quaternion differ in the last bits, and
+ *               on degenerate correspondences (fewer than 3, a line, one target row) in the rotation they pick.
+ *   range       target rows whose cell floor(x / cell_size) leaves [-2^20, 2^20) on an axis are left unmatched and raise a
+ *               flag on the device; icp_refine_end reads it and returns ICP_ERR_INVALID_ARGUMENT beside the filled result.
+ *               max_distance above 7 cells is searched exhaustively (every target row for every source row).
+ *   launches    icp_refine_set_target: clear, count, scan, scatter — a hashed uniform grid over the target with verified 64-bit
+ *               cell keys.  icp_refine_launch: max_iteration + 1 pairs of (fused move + search + reduce, one-workgroup solve);
+ *               once the loop has stopped on the device the remaining launches return at their first instruction.  No host
+ *               read before icp_refine_end, no float atomics: two runs of one call are bit-equal in every output.
+ *   footprint   24 bytes per target row + 16 per table slot (the power of two >= 2 max_target_rows, >= 64) + 4 per source row +
+ *               about 600 KB; + 12 per row of a cloud (and as much pinned host memory) once it has been given from host memory. */
+typedef struct icp_refine icp_refine;
+#define ICP_REFINE_DROP_ZERO_ROWS 1
+typedef struct {
+    double max_distance;     /* correspondence bound in metres (icp_distance_threshold) */
+    double relative_fitness; /* stop test on |fitness - previous fitness| */
+    double relative_rmse;    /* ... and on |inlier_rmse - previous inlier_rmse| */
+    int32_t max_iteration;   /* 0..1000 steps */
+    int32_t flags;           /* ICP_REFINE_DROP_ZERO_ROWS for the SOURCE rows */
+} icp_refine_params;
+typedef struct {
+    double transformation[16];    /* T [4,4] row-major, source into target (the reference's caller inverts it) */
+    double fitness, inlier_rmse;  /* of the last evaluation, which ran with T */
+    int64_t correspondences;      /* ... and its number of matched source rows */
+    int64_t source_rows;          /* counted source rows: the fitness denominator */
+    int64_t target_rows;          /* target rows that were not left out */
+    int64_t source_rows_left_out; /* rows ICP_REFINE_DROP_ZERO_ROWS took from the source */
+    int64_t target_rows_left_out; /* ... and from the target */
+    int32_t iterations;           /* steps taken */
+    int32_t converged;            /* 1: the stop test ended the loop, 0: max_iteration did */
+} icp_refine_result;
+/* the settings of the reference's call at slam/loop_closure.py:210-225: 1.0, 1e-6, 1e-6, 30 iterations, no flag */
+void icp_default_refine_params(icp_refine_params* params);
+/* a refiner for slam/loop_closure.py:210-225 with room for max_target_rows and max_source_rows rows and a search grid of
+ * cell_size metres (a matter of speed alone; the reference's bound, 1.0, is a good edge).  ICP_ERR_INVALID_ARGUMENT for a
+ * cell_size that is not positive and finite, a capacity < 1 or > 2^31 - 1, a NULL `out`. */
+int icp_refine_create(icp_ctx* ctx, int64_t max_target_rows, int64_t max_source_rows, double cell_size, icp_refine** out);
+/* waits for the refiner's work, then frees it (slam/loop_closure.py:210-225: no counterpart) */
+void icp_refine_destroy(icp_refine* refiner);
+/* the `target` cloud of slam/loop_closure.py:210-225: xyz [n,3] float32, `flags` ICP_REFINE_DROP_ZERO_ROWS or 0.  Asynchronous,
+ * four launches; host rows are copied into a pinned buffer of the refiner before the call returns, device rows are read in place and must stay untouched until the
+ * stream has passed the build.  n = 0 is legal (nothing matches).  ICP_ERR_INVALID_ARGUMENT, before any launch, for n < 0,
+ * n > max_target_rows, an unknown memory kind or flag, a refinement in flight. */
+int icp_refine_set_target(icp_refine* refiner, const float* xyz, int64_t n, int mem, int32_t flags);
+/* the registration_icp call of slam/loop_closure.py:210-225 on the `source` cloud xyz [n,3] float32 from `init` [4,4] float64
+ * (row-major): enqueues the whole loop and returns.  Device rows must stay untouched until icp_refine_end.  n = 0 is legal:
+ * fitness 0, inlier_rmse 0, 0 iterations, the transformation equals init.  ICP_ERR_INVALID_ARGUMENT, before any launch, for
+ * n < 0, n > max_source_rows, an unknown memory kind or flag, a max_distance that is not positive and finite (or whose square is
+ * not), max_iteration outside 0..1000, a negative threshold, a non-finite init entry, no target set, a refinement in flight. */
+int icp_refine_launch(icp_refine* refiner, const float* xyz, int64_t n, int mem, const double init[16], const icp_refine_params* params);
+/* waits for the refinement and returns what registration_icp does at slam/loop_closure.py:210-225 (`result` may be NULL);
+ * correspondence_out [n] int32 (host or device memory, may be NULL): the target row of every source row at the last evaluation,
+ * -1 without one.  ICP_ERR_INVALID_ARGUMENT with nothing launched, for an unknown memory kind, and — behind the filled result —
+ * when target rows lay outside +-2^20 cells. */
+int icp_refine_end(icp_refine* refiner, icp_refine_result* result, int32_t* correspondence_out, int out_mem);
+/* the rows of an elevation image for slam/loop_closure.py:210-225, IN PLACE: *xyz_out = the device pointer of the image's
+ * `points_3D` [H * W,3] float32, *n_out = H * W, to be passed on to icp_refine_set_target / icp_refine_launch as device memory
+ * with ICP_REFINE_DROP_ZERO_ROWS (empty pixels are all-zero rows).  No copy and no launch; the image must not be rebuilt or
+ * destroyed before the stream has passed the target build, or, for a source, before icp_refine_end.
+ * ICP_ERR_INVALID_ARGUMENT for a NULL image or output, an image of another context. */
+int icp_refine_image_rows(icp_refine* refiner, icp_elevation* image, const float** xyz_out, int64_t* n_out);
+/* the evaluations of the refinement icp_refine_end collected last (slam/loop_closure.py:210-225: Open3D keeps none):
+ * transforms_out [iterations + 1,16] and sums_out [iterations + 1,17] float64 in host memory, either may be NULL; `cap` = rows
+ * the outputs have room for.  ICP_ERR_INVALID_ARGUMENT for cap < iterations + 1 or before any icp_refine_end.  Synchronises. */
+int icp_refine_history(icp_refine* refiner, double* transforms_out, double* sums_out, int32_t cap);
+
 /* ---- profiling hooks ---------------------------------------------------------------------------------------------
  * Accumulated HIP-event time (ms) and launch count of the dominant kernel (the per-iteration nearest-neighbour
  * search) since the last reset; measured on the context's stream.  `enable` is a bit mask: 1 = search kernel,

@@ -306,6 +306,17 @@ int elevation_home(icp_elevation* e, void* user, const void* dev, size_t bytes, 
 
 }  // namespace
 
+namespace icp {
+
+// refine.hip reads the float32 point behind every pixel in place
+icp_ctx* elevation_context(icp_elevation* img) { return img->ctx; }
+const float* elevation_points_device(icp_elevation* img, int64_t* rows) {
+    *rows = img->height * img->width;
+    return img->points;
+}
+
+}  // namespace icp
+
 extern "C" {
 
 int icp_elevation_create(icp_ctx* ctx, int64_t height, int64_t width, double pixel_size, double z_min, double z_max, int flip,

@@ -678,6 +678,9 @@ void pmap_frame_loop_release(icp_ctx* ctx);
 // ---- batch_frame.hip
 void batch_frames_release(icp_batch* batch);
 
+// ---- elevation.hip: the context of an image and its device points [H * W][3] (refine.hip reads them in place)
+icp_ctx* elevation_context(icp_elevation* img);
+const float* elevation_points_device(icp_elevation* img, int64_t* rows);
 // ---- hash_grid.hip
 // defer != nullptr: everything but the launches — *defer receives their arguments (the caller launches them, e.g. for B maps
 // at once: launch_grid_build_batch) and calls build_grid_finish afterwards

@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpPmapFrameConfig", "IcpFrameResult", "IcpBatchFrame", "IcpAggmapCounters", "IcpElevationCounters", "load_library", "library_path",
+__all__ = ["IcpLibraryError", "IcpConfig", "IcpRegisterResult", "IcpPreprocessFrame", "IcpFrameConfig", "IcpPmapFrameConfig", "IcpFrameResult", "IcpBatchFrame", "IcpAggmapCounters", "IcpElevationCounters", "IcpRefineParams", "IcpRefineResult", "load_library", "library_path",
            "EXPORTED_SYMBOLS", "SCHEMES", "COSTS", "MEM_HOST", "MEM_DEVICE", "FRAME_ROWS", "FRAME_VERTEX_MAP", "TARGETS_ALL", "TARGETS_SKIP_NULL", "STATUS_MESSAGES"]
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -105,7 +105,23 @@ class IcpElevationCounters(C.Structure):
                 ("filled_pixels", C.c_int64)]
 
 
+class IcpRefineParams(C.Structure):
+    """icp_refine_params: the settings of one icp_refine_launch."""
+    _fields_ = [("max_distance", C.c_double), ("relative_fitness", C.c_double), ("relative_rmse", C.c_double),
+                ("max_iteration", C.c_int32), ("flags", C.c_int32)]
+
+
+class IcpRefineResult(C.Structure):
+    """icp_refine_result: what icp_refine_end returns."""
+    _fields_ = [("transformation", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("correspondences", C.c_int64), ("source_rows", C.c_int64), ("target_rows", C.c_int64),
+                ("source_rows_left_out", C.c_int64), ("target_rows_left_out", C.c_int64), ("iterations", C.c_int32),
+                ("converged", C.c_int32)]
+
+
 ELEVATION_F32, ELEVATION_F64 = 0, 1  # icp_elevation_dtype
+REFINE_DROP_ZERO_ROWS = 1  # ICP_REFINE_DROP_ZERO_ROWS
+REFINE_FIGURES = 17  # count, sum d2, mu_p [3], mu_q [3], H [9]
 ELEVATION_LUT_ROWS = 259
 
 _P = C.c_void_p
@@ -219,6 +235,14 @@ EXPORTED_SYMBOLS = {
     "icp_elevation_build_aggmap": (_INT, [_P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_double * 16)]),
     "icp_elevation_get": (_INT, [_P, _P, _P, _P, _P, _INT]),
     "icp_elevation_stats": (_INT, [_P, C.POINTER(IcpElevationCounters)]),
+    "icp_default_refine_params": (None, [C.POINTER(IcpRefineParams)]),
+    "icp_refine_create": (_INT, [_P, _I64, _I64, C.c_double, C.POINTER(_P)]),
+    "icp_refine_destroy": (None, [_P]),
+    "icp_refine_set_target": (_INT, [_P, _P, _I64, _INT, C.c_int32]),
+    "icp_refine_launch": (_INT, [_P, _P, _I64, _INT, C.POINTER(C.c_double * 16), C.POINTER(IcpRefineParams)]),
+    "icp_refine_end": (_INT, [_P, C.POINTER(IcpRefineResult), _P, _INT]),
+    "icp_refine_image_rows": (_INT, [_P, _P, C.POINTER(_P), C.POINTER(_I64)]),
+    "icp_refine_history": (_INT, [_P, _P, _P, C.c_int32]),
     "icp_normal_equations_ptr": (_P, [_P]),
     "icp_set_normal_equations_buffer": (_INT, [_P, _P]),
     "icp_profile_enable": (_INT, [_P, _INT]),

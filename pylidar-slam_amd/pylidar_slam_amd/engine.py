@@ -176,8 +176,9 @@ class IcpContext:
     # ------------------------------------------------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
-            for m in list(getattr(self, "_elevation_images", ())) + list(getattr(self, "_aggregated_maps", ())):
-                m.close()  # (an image or a map is destroyed before its context)
+            for m in list(getattr(self, "_cloud_refiners", ())) + list(getattr(self, "_elevation_images", ())) + \
+                    list(getattr(self, "_aggregated_maps", ())):
+                m.close()  # (a refiner, an image or a map is destroyed before its context)
             self._lib.icp_destroy(self._h)
             self._h = None
 
@@ -1023,6 +1024,11 @@ class IcpContext:
         of the reference with the settings of its constructor.  `color_map`: a matplotlib name, or a [259, 3] uint8 table."""
         return ElevationImage(self, height, width, pixel_size, z_min, z_max, flip_z_axis, color_map, max_rows)
 
+    def cloud_refiner(self, max_target_rows: int, max_source_rows: int, cell_size: float = 1.0) -> "CloudRefiner":
+        """A cloud-to-cloud point-to-point ICP on this context's device (`icp_refine_*`): the Open3D refinement of the
+        reference's loop closure (slam/loop_closure.py:210-225), with a search grid of its own of `cell_size` metres."""
+        return CloudRefiner(self, max_target_rows, max_source_rows, cell_size)
+
     def raise_for_status(self, rc: int):
         """Maps a status code of the C ABI to the exception the reference raises (public form of the internal check)."""
         self._check(rc)
@@ -1334,6 +1340,134 @@ class ElevationImage:
         [H, W]}), on the host."""
         self.build(pc)
         return self.rgb, {"points_3D": self.points_3d, "pc_indices": self.indices.astype(np.int64)}
+
+
+class RefineResult:
+    """What `CloudRefiner.end` returns (icp_refine_result): `transformation` [4, 4] float64 (source into target), `fitness`,
+    `inlier_rmse`, `iterations`, `converged`, the counters `num_correspondences`, `source_rows`, `target_rows`,
+    `source_rows_left_out`, `target_rows_left_out`, and `correspondences` [n] int32 (the target row of every source row at the
+    last evaluation, -1 without one), copied from the device when first read."""
+
+    def __init__(self, res: "_lib.IcpRefineResult", n: int, fetch):
+        self.transformation = np.array(res.transformation, np.float64).reshape(4, 4)
+        self.fitness, self.inlier_rmse = float(res.fitness), float(res.inlier_rmse)
+        self.iterations, self.converged = int(res.iterations), bool(res.converged)
+        self.num_correspondences, self.source_rows, self.target_rows = int(res.correspondences), int(res.source_rows), int(res.target_rows)
+        self.source_rows_left_out, self.target_rows_left_out = int(res.source_rows_left_out), int(res.target_rows_left_out)
+        self._n, self._fetch, self._corr = int(n), fetch, None
+
+    @property
+    def correspondences(self) -> np.ndarray:
+        if self._corr is None:
+            self._corr = self._fetch(self._n)
+            self._fetch = None
+        return self._corr
+
+
+class CloudRefiner:
+    """`ElevationImageLoopClosure._compute_transform` of the reference (slam/loop_closure.py:210-225) on the device
+    (`icp_refine_*`, include/icp_mi355x.h): Open3D's point-to-point `registration_icp` of a source cloud against a target cloud.
+
+    `set_target(rows)` builds the refiner's own search grid; `launch(rows, init, ...)` enqueues the whole loop and returns,
+    `end()` waits and returns a `RefineResult`, `refine(...)` is both, `history()` the T and the 17 figures of every
+    evaluation.  Rows are [n, 3] float32 (numpy: copied in; cuda tensor: read in place) or an `ElevationImage`, whose device
+    `points_3D` is read in place (no copy: do not rebuild the image before `end`), the all-zero rows of empty pixels left out.  Nothing here touches the context's map or a
+    registration in flight.  Create it with `IcpContext.cloud_refiner`."""
+
+    def __init__(self, ctx: "IcpContext", max_target_rows: int, max_source_rows: int, cell_size: float = 1.0):
+        self._ctx, self._lib, self._h = ctx, ctx._lib, None
+        self.max_target_rows, self.max_source_rows, self.cell_size = int(max_target_rows), int(max_source_rows), float(cell_size)
+        self._keep_target = self._keep_source = None
+        self._n, self._last, self._corr_dev = 0, None, None
+        h = C.c_void_p()
+        ctx._check(self._lib.icp_refine_create(ctx._h, self.max_target_rows, self.max_source_rows, self.cell_size, C.byref(h)))
+        self._h = h
+        if not hasattr(ctx, "_cloud_refiners"):
+            ctx._cloud_refiners = weakref.WeakSet()
+        ctx._cloud_refiners.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
+            self._lib.icp_refine_destroy(self._h)
+        self._h = self._keep_target = self._keep_source = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not self._h:
+            raise AssertionError("the cloud refiner has been closed")
+        return self._h
+
+    def _rows(self, rows, drop_zero_rows: bool, who: str):
+        """(pointer, n, mem, keep-alive, drop flag) of a cloud: an ElevationImage's device points_3D, or [n, 3] float32 rows"""
+        if isinstance(rows, ElevationImage):
+            if rows._ctx is not self._ctx:
+                raise AssertionError(f"CloudRefiner.{who}: the elevation image belongs to another context")
+            self._ctx.use_torch_stream()
+            ptr, n = C.c_void_p(), C.c_int64(0)
+            self._ctx._check(self._lib.icp_refine_image_rows(self._handle(), rows._handle(), C.byref(ptr), C.byref(n)))
+            return ptr.value, int(n.value), MEM_DEVICE, rows, True  # (read in place: the image is kept alive, no copy is made)
+        self._ctx._bind(rows)
+        p, mem, keep = _ptr_mem(rows)
+        if keep.ndim != 2 or keep.shape[1] != 3:
+            raise AssertionError(f"CloudRefiner.{who}: expected [n, 3] points, got {tuple(keep.shape)}")
+        n = int(keep.shape[0])
+        return (p if n else None), n, mem, keep, bool(drop_zero_rows)
+
+    def set_target(self, rows, drop_zero_rows: bool = False) -> None:
+        """The target cloud (`target_pc` of the reference); asynchronous."""
+        h = self._handle()
+        p, n, mem, keep, drop = self._rows(rows, drop_zero_rows, "set_target")
+        self._ctx._check(self._lib.icp_refine_set_target(h, p, n, mem, _lib.REFINE_DROP_ZERO_ROWS if drop else 0))
+        self._keep_target = keep if mem == MEM_DEVICE else None
+
+    def launch(self, rows, init=None, max_distance: float = 1.0, max_iteration: int = 30, relative_fitness: float = 1e-6,
+               relative_rmse: float = 1e-6, drop_zero_rows: bool = False) -> None:
+        """Enqueues the refinement of the source cloud `rows` (`candidate_pc`) from `init` [4, 4] (the identity by default) with
+        the defaults of the reference's call; returns at once."""
+        h = self._handle()
+        p, n, mem, keep, drop = self._rows(rows, drop_zero_rows, "launch")
+        prm = _lib.IcpRefineParams(float(max_distance), float(relative_fitness), float(relative_rmse), int(max_iteration),
+                                   _lib.REFINE_DROP_ZERO_ROWS if drop else 0)
+        t0 = _pose16_f64(np.eye(4) if init is None else init)
+        self._ctx._check(self._lib.icp_refine_launch(h, p, n, mem, C.byref(t0), C.byref(prm)))
+        self._keep_source, self._n = keep, n
+
+    def end(self) -> RefineResult:
+        """Waits for the refinement launched last and returns its `RefineResult`."""
+        h = self._handle()
+        res = _lib.IcpRefineResult()
+        self._ctx.use_torch_stream()
+        corr = torch.empty(max(self._n, 1), dtype=torch.int32, device=self._ctx.device)
+        rc = self._lib.icp_refine_end(h, C.byref(res), corr.data_ptr() if self._n else None, MEM_DEVICE)
+        self._keep_source = None
+        self._ctx._check(rc)
+        self._corr_dev = corr
+        self._last = RefineResult(res, self._n, lambda n, c=corr: c[:n].cpu().numpy() if n else np.empty(0, np.int32))
+        return self._last
+
+    def correspondences_device(self) -> torch.Tensor:
+        """the correspondences of the refinement collected last as an int32 cuda tensor [n]"""
+        return self._corr_dev[:self._n]
+
+    def refine(self, rows, **kw) -> RefineResult:
+        """`launch(rows, **kw)` followed by `end()`."""
+        self.launch(rows, **kw)
+        return self.end()
+
+    def history(self):
+        """(transforms [iterations + 1, 4, 4], figures [iterations + 1, 17]) float64 of the refinement collected last: for every
+        evaluation the T it ran with and count, sum d2, mu_p [3], mu_q [3], H [9]."""
+        if self._last is None:
+            raise AssertionError("CloudRefiner.history: no refinement has been collected")
+        rows = self._last.iterations + 1
+        t, s = np.empty((rows, 16), np.float64), np.empty((rows, _lib.REFINE_FIGURES), np.float64)
+        self._ctx._check(self._lib.icp_refine_history(self._handle(), t.ctypes.data, s.ctypes.data, rows))
+        return t.reshape(rows, 4, 4), s
 
 
 class IcpBatch:

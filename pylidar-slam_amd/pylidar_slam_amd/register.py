@@ -171,3 +171,67 @@ def install_elevation_image(factory=None):
     build_image.__doc__ = "Builds an elevation image (on the MI355X: pylidar_slam_amd.register.install_elevation_image)"
     cls.build_image = build_image
     return cls
+
+
+class _DeviceCloudRefiner:
+    """The default refiner of `install_loop_closure_refinement`: a `CloudRefiner` on a context shared by all of them, recreated
+    with more room when a cloud has more rows than it takes."""
+    _ctx = None
+
+    def __init__(self, owner=None):
+        self.owner, self.refiner = owner, None
+
+    def refine(self, candidate_pc, target_pc, initial_transform, max_distance):
+        from .engine import IcpContext
+        rows_t, rows_s = int(target_pc.shape[0]), int(candidate_pc.shape[0])
+        r = self.refiner
+        if r is None or rows_t > r.max_target_rows or rows_s > r.max_source_rows:
+            if _DeviceCloudRefiner._ctx is None:
+                _DeviceCloudRefiner._ctx = IcpContext()
+            if r is not None:
+                r.close()
+            room = 1 << max(17, (max(rows_t, rows_s, 1) - 1).bit_length())
+            r = self.refiner = _DeviceCloudRefiner._ctx.cloud_refiner(room, room, 1.0)
+        r.set_target(target_pc)
+        return r.refine(candidate_pc, init=initial_transform, max_distance=max_distance)
+
+
+def compute_transform(self, initial_transform, candidate_pc, target_pc, factory=None):
+    """`ElevationImageLoopClosure._compute_transform` (slam/loop_closure.py:210-225) on the MI355X: the point-to-point ICP of
+    `candidate_pc` against `target_pc` from `initial_transform`, bound `self.config.icp_distance_threshold` (1.0 where `self`
+    has no such setting), 30 iterations, 1e-6 / 1e-6; returns `(np.linalg.inv(T), candidate_pc, target_pc)` as the reference
+    does, the inverse taken on the host in float64.  `self` keeps its refiner (made by `factory(self)`, by default a
+    `CloudRefiner` on a shared context); any object that takes attributes will do."""
+    import numpy as np
+    held = getattr(self, "_mi355x_refiner", None)
+    if held is None:
+        held = (factory or _DeviceCloudRefiner)(self)
+        self._mi355x_refiner = held
+    bound = float(getattr(getattr(self, "config", None), "icp_distance_threshold", 1.0))
+    result = held.refine(np.ascontiguousarray(candidate_pc, dtype=np.float32), np.ascontiguousarray(target_pc, dtype=np.float32),
+                         np.asarray(initial_transform, dtype=np.float64), bound)
+    return np.linalg.inv(result.transformation), candidate_pc, target_pc
+
+
+def install_loop_closure_refinement(factory=None):
+    """Assigns the reference's `ElevationImageLoopClosure` (slam/loop_closure.py:122-; the class exists only where `cv2` does)
+    the `_compute_transform` above, and switches the module's Open3D guard (`_with_o3d`, tested at :237) on.  The config field
+    `EILoopClosureConfig.with_icp_refinement` took its default from that guard when the class was defined: without Open3D it is
+    False and has to be set to True by the user for the refinement to run.  `factory(instance)` returns an object with `refine(candidate_pc, target_pc, initial_transform,
+    max_distance)` whose result has a `transformation`.  Returns the patched class, or None where the reference does not define
+    it."""
+    try:
+        import slam.loop_closure as ref_loop_closure
+    except ImportError:
+        return None
+    cls = getattr(ref_loop_closure, "ElevationImageLoopClosure", None)
+    if cls is None:
+        return None
+
+    def _compute_transform(self, initial_transform, candidate_pc, target_pc):
+        return compute_transform(self, initial_transform, candidate_pc, target_pc, factory)
+
+    _compute_transform.__doc__ = "Refines the 2-D alignment (on the MI355X: pylidar_slam_amd.register.install_loop_closure_refinement)"
+    cls._compute_transform = _compute_transform
+    ref_loop_closure._with_o3d = True
+    return cls
