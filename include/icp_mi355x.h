@@ -187,6 +187,15 @@ int icp_synchronize(icp_ctx* ctx);
  *   "wide_until" n (3)              the launches of ICP iterations below n run 1024 threads per 512 queries (two lanes for every
  *                                   miss even when all 512 search: the slowest wave of a launch is a lane walking the candidates
  *                                   of a dense cell alone); same bits
+ *   "first_build" 0 | 1 (1)         icp_register_launch / icp_register_launch_from_last / icp_frame_launch of ONE sequence: ICP
+ *                                   iteration 0 runs a build of the fused kernel of its own, which reads the scan rows itself,
+ *                                   packs them for the later launches and initialises the registration state — no packing
+ *                                   launch in front of it, no miss list in front of its searches (every query of that launch
+ *                                   searches).  Taken with fused iterations, normals at hand (eager or carried), "ball_search",
+ *                                   the 512-query shapes ("narrow_from" 0; "wide_until" > 0 with "ball_lanes" >= 2), and without
+ *                                   the in-library exchange, "hit_records", "lazy_fused", "search_stats" and the event profile;
+ *                                   otherwise, and with 0, the packing launch and the generic kernel run
+ *                                   (icp_first_build_launches counts the registrations that took it); same bits
  *   "ball_max" n (256; <= 256)      ... if own cell + surviving cells hold at most n candidates: one lane walks them alone, and the
  *                                   longest walk of a launch sets its duration (heavier queries: the cooperative searches)
  *   "chunked_launch" 0 | 1 (1)      icp_register_launch with threshold_delta_pose > 0 enqueues as many iterations as the last
@@ -397,6 +406,9 @@ int icp_map_num_clouds(const icp_ctx* ctx);
  * of its wall-clock budget ("resident_tail", "lead_solve": a GPU shared with foreign work); the first one switches the
  * context to per-iteration launches for good — results are unaffected (diagnostics; no reference counterpart) */
 int icp_handoff_fallbacks(const icp_ctx* ctx);
+/* registrations of this context whose first launch was the first-iteration build (option "first_build") instead of the packing
+ * launch + the generic kernel (diagnostics; no reference counterpart) */
+int icp_first_build_launches(const icp_ctx* ctx);
 int icp_map_get(icp_ctx* ctx, float* xyz_out, int out_mem); /* current map [M,3] in insertion order */
 /* nearest_neighbor_search() :372-395 + __get_normals :397-422 — exact Euclidean 1-NN (no distance cap) and the
  * lazily estimated normal of every hit.  Outputs [n,3], [n,3], [n] (any may be NULL). */

@@ -396,6 +396,7 @@ int icp_set_option(icp_ctx* ctx, const char* name, double value) {
     else if (k == "resident_tail_max_blocks") ctx->resident_tail_max_blocks = iv < 0 ? 0 : (int)iv;
     else if (k == "ball_search") ctx->ball_search = value != 0.0 ? 1 : 0;
     else if (k == "wide_until") ctx->wide_until = iv < 0 ? 0 : (int)iv;
+    else if (k == "first_build") ctx->first_build = iv != 0 ? 1 : 0;
     else if (k == "far_lanes") ctx->far_lanes = iv >= 16 ? 16 : 0;
     else if (k == "far_min") ctx->far_min = iv < 0 ? 0 : (int)iv;
     else if (k == "far_max") ctx->far_max = iv < 0 ? 0 : (iv > 512 ? 512 : (int)iv);
@@ -1012,6 +1013,7 @@ int icp_map_update_vertex_map(icp_ctx* ctx, const float rel_pose[16], const floa
 
 int64_t icp_map_size(const icp_ctx* ctx) { return ctx ? ctx->map_m : 0; }
 int icp_handoff_fallbacks(const icp_ctx* ctx) { return ctx ? ctx->handoff_fallbacks : 0; }
+int icp_first_build_launches(const icp_ctx* ctx) { return ctx ? ctx->first_launches : 0; }
 int icp_map_num_clouds(const icp_ctx* ctx) { return ctx ? (int)ctx->cloud_sizes.size() : 0; }
 
 int icp_map_get(icp_ctx* ctx, float* xyz_out, int out_mem) {

@@ -1231,7 +1231,23 @@ int prepare_targets(icp_ctx* ctx, const float* xyz_dev, int64_t n, const Pose16*
         *defer = d;
         return ICP_OK;
     }
-    hipLaunchKernelGGL(k_pack_targets, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d.xyz, d.n, d.out, d.st,
+    return launch_pack_targets(ctx, d);
+}
+
+// A registration that begins with k_iterate_first never launches k_pack_targets — and the runtime loads the code of a source
+// file when one of its kernels is first asked for: the first registration to fall back (the event profile switched on in the
+// middle of a sequence, say) would pay that load inside a frame.  Measured (profiles/first_iteration_ab.txt, section G): the
+// `--full` line of bench.py switches the event profile on behind its warm-up — without the preload ONE step of its 60 took
+// 4.06 ms (headline 2465-2514 against the parent's 2932-2946 scans/s), with it none (2941-2949 against 2933-2942).  Asking
+// for the kernel's attributes loads it now, in the first registration of the context, where the parent paid for it too.
+void pack_targets_preload() {
+    hipFuncAttributes attr;
+    (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(k_pack_targets));
+}
+
+int launch_pack_targets(icp_ctx* ctx, const PackDesc& d) {
+    if (d.n <= 0) return ICP_OK;
+    hipLaunchKernelGGL(k_pack_targets, dim3((unsigned)((d.n + 255) / 256)), dim3(256), 0, ctx->stream, d.xyz, d.n, d.out, d.st,
                        d.init, d.keep_pose, d.box, d.gen, d.hist);
     ICP_HIP(ctx, hipGetLastError());
     return ICP_OK;

@@ -148,6 +148,9 @@ struct LeadArgs {
 // Call with all 64 lanes of a wave active; `lane` = lane index.
 // keep_pose: the initial guess is the pose the state already holds — the result of the previous registration, i.e. the
 // constant-velocity initialisation (slam/initialization.py:103-119) without a host round trip.
+// INVARIANT k_iterate_first (search.hip) relies on: with keep_pose, pose[0..15] is written back with the very bits that were
+// read, one aligned dword store per word, and nothing else is ever stored into pose[] here — the other workgroups of that
+// launch read pose[0..11] for their transform while this wave runs, without waiting for it.
 __device__ inline void state_init_wave(RegState* st, const float* init, int keep_pose, unsigned long long* __restrict__ box,
                                        unsigned gen, float* __restrict__ hist, int lane) {
     float p = 0.f;
@@ -497,6 +500,15 @@ struct icp_ctx {
     int chunked_launch = 1;            // "chunked_launch": launched registrations with a live threshold are enqueued in chunks
     int ball_search = 1;               // "ball_search": NN-cache misses of the fused kernel searched by one lane each first (search_ball_lane)
     int wide_until = 3;                // "wide_until": fused launches of iterations below that run with 1024 threads per 512 queries
+    // "first_build": iteration 0 of a launched registration of one sequence runs k_iterate_first (search.hip), which packs the
+    // targets and initialises the state itself — no k_pack_targets launch in front of it.  register_begin holds the packing
+    // launch back (`first_pending`, its arguments in `first_pack`); launch_iterate_fused either folds it into the first
+    // launch or, where that launch is not one the build exists for, runs it after all
+    int first_build = 1;
+    bool first_pending = false;
+    bool first_pack_preloaded = false;  // k_pack_targets' code has been loaded for the fall-backs of this context
+    icp::PackDesc first_pack{};
+    int first_launches = 0;            // registrations of this context that began with k_iterate_first (icp_first_build_launches)
     int far_lanes = 16;                // "far_lanes": 16 lanes for a query the ball search hands back, where a workgroup has a few dozen (0 | 16)
     int far_min = 16;                  // "far_min": ... more than that many (fewer: a wave each)
     int far_max = 128;                 // "far_max": ... up to that many of them (THREADS / 16 at a time)
@@ -842,6 +854,8 @@ int distort_device(icp_ctx* ctx, const float* xyz_dev, const double* ts_dev, int
 // guess; keep_pose: the pose the state already holds — the previous result — is the guess)
 int prepare_targets(icp_ctx* ctx, const float* xyz_dev, int64_t n, const Pose16* init = nullptr, bool keep_pose = false,
                     PackDesc* defer = nullptr);  // defer: the launch is left to the caller (launch_pack_targets_batch)
+int launch_pack_targets(icp_ctx* ctx, const PackDesc& d);  // ... of ONE registration, from the descriptor prepare_targets left
+void pack_targets_preload();  // (loads k_pack_targets' code without launching it: a context's first held-back packing launch)
 int launch_pack_targets_batch(icp_ctx* first, const PackDesc* table_host, const PackDesc* table_dev, int count);
 int voxel_statistics_device(icp_ctx* ctx, const float* xyz_dev, int64_t n, double voxel, long long* voxels_dev,
                             long long* hashes_dev, long long* ids_dev, long long* sizes_dev, float* means_dev,
@@ -916,7 +930,8 @@ void pmap_window_step(icp_ctx* ctx, const float rel_pose[16], int slot);
 // register.hip: the two begins, the result hand-over and the iterations a chunked launch holds back
 bool fused_path(const icp_ctx* ctx);
 int register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16],
-                   bool from_last, icp::PackDesc* defer_pack = nullptr);
+                   bool from_last, icp::PackDesc* defer_pack = nullptr, bool hold_pack = false);
+int first_pack_flush(icp_ctx* ctx);  // the packing launch register_begin held back for k_iterate_first ("first_build"), if still pending
 int pmap_register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16],
                         bool from_last, icp::PackDesc* defer_pack, bool pose_now);
 void result_fold_reset(icp_ctx* ctx);

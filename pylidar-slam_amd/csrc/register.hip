@@ -70,8 +70,25 @@ int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int ta
 // ---- registration ---------------------------------------------------------------------------------------------------
 // defer_pack: the launch that packs the targets and initialises the state is left to the caller (a batched registration runs
 // it for all its members at once)
+// hold_pack (icp_register_launch: the iterations are enqueued right behind the begin): with option "first_build", and where the
+// first launch of the registration will be a fused iteration of one sequence with its normals at hand, the packing launch is
+// held back in ctx->first_pack — launch_iterate_fused folds it into k_iterate_first, or runs it in front of a launch that
+// build does not exist for (first_pack_flush: whoever enqueues anything else first)
+static bool first_build_wanted(const icp_ctx* ctx, int64_t n) {
+    return ctx->first_build && n > 0 && ctx->cfg.max_num_alignments >= 1 &&
+           ctx->cost == ICP_COST_POINT_TO_PLANE && ctx->fuse_iteration && (ctx->normals_ready || wants_eager_normals(ctx, n)) &&
+           !wants_lazy_fused(ctx, n) && !ctx->exchange_on && !ctx->search_stats && !ctx->prof.enabled && ctx->ball_search &&
+           !(ctx->hit_records && ctx->use_nn_cache);
+}
+
+int first_pack_flush(icp_ctx* ctx) {
+    if (!ctx->first_pending) return ICP_OK;
+    ctx->first_pending = false;
+    return launch_pack_targets(ctx, ctx->first_pack);
+}
+
 int register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16],
-                   bool from_last, PackDesc* defer_pack) {
+                   bool from_last, PackDesc* defer_pack, bool hold_pack) {
     if (!ctx || n < 0 || (n > 0 && !xyz)) return ICP_ERR_INVALID_ARGUMENT;
     if (ctx->map_m <= 0 || !ctx->grid_valid) return fail(ctx, ICP_ERR_EMPTY_MAP, "the local map is empty");
     if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
@@ -80,7 +97,14 @@ int register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int targe
     int rc = ensure_state(ctx);
     if (rc || (rc = stage_targets(ctx, xyz, n, mem, target_mode))) return rc;
     ICP_HIP(ctx, ctx->nn_pos.reserve((size_t)(n > 0 ? n : 1) * 4));
-    if ((rc = prepare_targets_and_state(ctx, n, init_pose, from_last, defer_pack))) return rc;
+    ctx->first_pending = false;
+    const bool hold = hold_pack && !defer_pack && first_build_wanted(ctx, n);
+    if ((rc = prepare_targets_and_state(ctx, n, init_pose, from_last, hold ? &ctx->first_pack : defer_pack))) return rc;
+    ctx->first_pending = hold;
+    if (hold && !ctx->first_pack_preloaded) {  // (once per context: a later fall-back finds the packing kernel loaded)
+        pack_targets_preload();
+        ctx->first_pack_preloaded = true;
+    }
     ctx->have_device_pose = true; ctx->device_pose_epoch += 1;
     // event pairs around the kernels of every `every`-th registration only: a pair costs ~2 us of stream time
     ctx->prof.sample_now = ctx->prof.every <= 1 || (ctx->prof.registrations % ctx->prof.every) == 0;
@@ -92,6 +116,8 @@ int register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int targe
     if (!ctx->normals_ready && wants_eager_normals(ctx, n) && (rc = launch_normals_all(ctx))) return rc;
     // ... or on demand inside the fused iteration kernel, where the scan touches a small part of the map ("lazy_fused")
     ctx->lazy_now = !ctx->normals_ready && wants_lazy_fused(ctx, n);
+    // (a held packing launch whose registration turns out not to begin with a plain fused iteration after all: now)
+    if (ctx->first_pending && (!fused_path(ctx) || ctx->lazy_now) && (rc = first_pack_flush(ctx))) return rc;
     registering_enter(ctx);
     // lead launches or not: decided ONCE per registration (another context of the process starting or ending a
     // registration between two chunks of this one flipped the answer — a chunk without a lead publishes no pose, the next
@@ -449,7 +475,7 @@ static int register_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, i
     if (ctx->r_count >= 2) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "two results are already pending");
     int rc = continue_launch(ctx, -1);  // (an older launch still holding iterations back: they come first on the stream)
     if (rc) return rc;
-    rc = register_begin(ctx, xyz, n, mem, target_mode, init_pose, from_last);
+    rc = register_begin(ctx, xyz, n, mem, target_mode, init_pose, from_last, nullptr, true);
     if (rc) return rc;
     // forced iteration count (threshold <= 0): every iteration is enqueued.  Live threshold: a first chunk of as many
     // iterations as the last frame ran plus one (launches behind an early stop would see `done` on the device and return
@@ -461,7 +487,10 @@ static int register_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, i
     const int first_chunk = first_chunk_iterations(iters, ctx->cfg.threshold_delta_pose, ctx->chunked_launch, tail,
                                                    &ctx->last_iterations, 1);
     rc = result_fold_begin(ctx, false);  // (the last solving launch of the chunk delivers the result block itself)
+    // (a first chunk holds at least one iteration — first_chunk_iterations — so launch 0 is never held back by the chunking)
     if (!rc) rc = enqueue_iterations(ctx, false, 0, first_chunk);
+    if (!rc) rc = first_pack_flush(ctx);  // (nothing unless no fused launch took it over)
+    ctx->first_pending = false;
     return result_hand_over(ctx, rc, first_chunk, iters - first_chunk);
 }
 

@@ -1369,6 +1369,18 @@ struct IterInputs {
     int swz_row_blocks;      // blocks per image row
 };
 
+// What the FIRST build of the launch (k_iterate_first: iteration 0 of a registration, no packing launch in front of it) takes
+// beside the generic arguments: the scan rows it packs itself and the arguments of state_init_wave (PackDesc's fields)
+struct FirstArgs {
+    const float* xyz = nullptr;  // [n,3] rows of the scan
+    float4* tgt_out = nullptr;   // = IterInputs.tgt, writable: (x, y, z, bits(row)) for the launches behind this one
+    Pose16 init{};               // the initial guess (keep_pose: the RegState's pose instead)
+    int keep_pose = 0;
+    unsigned gen = 0;            // generation of the pose mailbox the initial guess is published as
+    unsigned long long* box = nullptr;
+    float* hist = nullptr;
+};
+
 // logical workgroup of physical workgroup `p` (`off` = 1 when workgroup 0 is the lead of a lead launch)
 __device__ inline int logical_block(const IterInputs& in, int p, int off) {
     if (in.swz_bpr_shift < 0) return p - off;
@@ -1577,10 +1589,22 @@ __device__ inline void normal_from_cov(const float* __restrict__ cov, int s, flo
 // workgroup is the lead of its sequence (block-uniform); `pb` / `off`: its physical number among the workgroups of the
 // sequence and the number of lead workgroups in front of them (logical_block); `bx` / `gx`: blockIdx.x / gridDim.x of a
 // launch that holds ONE sequence (the resident tail, the dev stamps).
-template <int THREADS, int Q, bool STATS, bool TAIL, int LAZY_KN, bool REC_BUILD>
+// FIRST (k_iterate_first): iteration 0 of a registration as a build of its own, WITHOUT a packing launch in front of it.
+// Every query of that launch searches (no NN cache yet), so the build carries no cache test, no pose history, no mailbox
+// poll, no lead and no miss list in front of the ball search: local slot s is searched by lanes s * LPQ .. s * LPQ + LPQ - 1
+// (LPQ = THREADS / Q: what the generic build gives a workgroup whose Q queries all miss), each of which reads the scan row
+// itself — target, transformed point and seed never leave its registers; lane 0 of the group packs the row into the target
+// buffer for the later launches.  The first wave of workgroup 0 initialises the registration state (state_init_wave, as
+// k_pack_targets would); nobody reads what it writes: the pose comes from the kernel arguments, or (keep_pose) from the
+// RegState the wave itself copies it from.  What the ball search hands back goes on the miss list for phases BF / B1 / B2
+// as in the generic build: same neighbours, same entries, same rows in the same slots — the same bits.
+template <int THREADS, int Q, bool STATS, bool TAIL, int LAZY_KN, bool REC_BUILD, bool FIRST = false>
 __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState* __restrict__ st, AlignParams ap,
                                              LeadArgs lead, const bool is_lead, const int pb, const int off, const int bx,
-                                             const int gx) {
+                                             const int gx, const FirstArgs fa = FirstArgs{}) {
+    static_assert(!FIRST || (!STATS && !TAIL && LAZY_KN == 0 && !REC_BUILD && Q == IT_THREADS && (THREADS == Q || THREADS == 2 * Q)),
+                  "the first-iteration build exists for the two 512-query shapes of the plain kernel");
+    constexpr int FLPQ = FIRST ? THREADS / Q : 1;  // FIRST: lanes per query
     if (!STATS) {  // (constant-folds every `if (g.dbg)` / `if (stamps)` below and inside the inlined searches)
         g.dbg = nullptr;
         g.stamps = nullptr;
@@ -1607,7 +1631,9 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
     // placed before it (a role ticket drawn from a counter would make that independent of the dispatch order — and costs
     // a thousand same-address device-scope atomics per launch, ~10 us: measured); should the order ever differ, the
     // wall-clock bound of the poll turns the wait into ICP_ERR_HIP instead of a hang.
-    if (lead.box) {
+    if constexpr (FIRST) {
+        // (nothing to solve in front of iteration 0, and the loop cannot have ended: `done` is being reset by this launch)
+    } else if (lead.box) {
         if (is_lead) {  // block-uniform
             lead_solve<THREADS>(lead, st, ap, reinterpret_cast<double*>(&cellstack[0][0]),
                                 (g.stamps && in.iter < 24) ? g.stamps + 4 * ((size_t)in.iter * 1024 + 1023) : nullptr);
@@ -1634,7 +1660,7 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
     if (g.dbg) g.dbg = dbg_s;  // the search paths count into LDS (flat atomics); flushed, and stored per workgroup, at the end
     // (TAIL: the poses of the iterations this launch runs come from the mailbox and are kept in hist_s by the workgroup
     // itself — the lead's stores to pose_hist are for later launches and the host)
-    if (in.use_cache && (int)threadIdx.x < 12 * CACHE_HIST) {
+    if (!FIRST && in.use_cache && (int)threadIdx.x < 12 * CACHE_HIST) {
         const int e = threadIdx.x / 12, j = in.iter - 1 - e;  // iteration j, most recent first
         if (j >= 0) hist_s[j % CACHE_HIST][threadIdx.x % 12] = in.pose_hist[(size_t)j * 12 + threadIdx.x % 12];
     }
@@ -1653,10 +1679,33 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
 #pragma unroll 1
     for (int tj = 0;; ++tj) {  // (one trip unless TAIL)
     const LocalTid threadIdx = TAIL ? reloaded_tid() : LocalTid{::threadIdx.x};  // (icp_internal.h)
-    const int lq = threadIdx.x, qi = query_of(lq);
+    // (FIRST: FLPQ neighbouring lanes stand for one slot, `fsub` = this lane's place among them)
+    const int lq = (int)threadIdx.x / FLPQ, fsub = (int)threadIdx.x % FLPQ, qi = query_of(lq);
     const int iter_now = in.iter + tj;  // (= the RegState's / the mailbox's iteration count while the loop is running)
     const unsigned gen_now = lead.gen + (unsigned)tj;
-    if (lq < Q && need_load) {
+    if constexpr (FIRST) {
+        // the scan row itself, by every lane of the slot (one address: one transaction); lane 0 packs it for launches 1..
+        valid = qi < in.n;
+        if (valid) {
+            t4 = make_float4(fa.xyz[3 * (size_t)qi], fa.xyz[3 * (size_t)qi + 1], fa.xyz[3 * (size_t)qi + 2], __int_as_float(qi));
+            valid = target_valid(t4.x, t4.y, t4.z, in.mode);
+            if (fsub == 0) {
+                fa.tgt_out[qi] = t4;
+                if (!valid) in.nn_cache[qi] = make_int4(-1, 0, -1, -1);  // masked row: no neighbour, no seed
+            }
+        }
+        if (valid && in.frame_seed) {
+            const int o = in.frame_seed[qi];
+            if (o >= 0 && o < g.m) {
+                seed_o = o;
+                seed_sp = g.pos_of_orig[o];
+                cq = g.pts[seed_sp];
+            }
+        }
+        // the registration state, generation `gen` of the pose mailbox and entry 0 of the pose history: for the launches
+        // behind this one and for the host (nobody in this launch reads them)
+        if (bx == 0 && threadIdx.x < 64) state_init_wave(st, fa.init.m, fa.keep_pose, fa.box, fa.gen, fa.hist, (int)threadIdx.x);
+    } else if (lq < Q && need_load) {
         need_load = false;
         c = make_int4(-1, 0, -1, -1);
         r1.w = __int_as_float(-1);
@@ -1701,14 +1750,19 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
     // ---- the pose: from the mailbox (lead launch) or from the RegState (classic launch)
     if (threadIdx.x < 4) ctl_s[threadIdx.x] = threadIdx.x == 0 ? vb : 0;
     if (dbg_global && threadIdx.x < 16) dbg_s[threadIdx.x] = 0;
-    __syncthreads();
+    if constexpr (!FIRST) __syncthreads();  // (FIRST: nothing below reads ctl_s before the barrier behind the pose)
     if (TAIL && bx == 0) {  // (block-uniform) the lead: solve tj, published as generation gen_now, in front of its own share
         if (!tail_lead_step<THREADS>(lead, st, ap, reinterpret_cast<double*>(&cellstack[0][0]), carry_s, tj, gen_now, in.tail_rows,
                                      gx,
                                      (g.stamps && iter_now < 24) ? g.stamps + 4 * ((size_t)iter_now * 1024 + 1023) : nullptr))
             return;
     }
-    if (lead.box) {
+    if constexpr (FIRST) {
+        // the initial guess: from the arguments, or (keep_pose) from the RegState — the words the initialising wave of
+        // workgroup 0 reads and writes back unchanged (the invariant stated at state_init_wave, icp_internal.h: same bits, one
+        // aligned dword per word, so whichever of the two a reader sees is the guess)
+        if (threadIdx.x < 12) pose_s[threadIdx.x] = fa.keep_pose ? st->pose[threadIdx.x] : fa.init.m[threadIdx.x];
+    } else if (lead.box) {
         if (threadIdx.x < BOX_USED) {
             const unsigned long long* p = box_granule(lead.box, gen_now, vb % BOX_REPLICAS, threadIdx.x);
             const long long t0 = wall_clock64();
@@ -1736,19 +1790,19 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
     }
     __syncthreads();
 
-    if (ctl_s[3]) {  // never seen: the hand-off did not arrive within its wall-clock budget -> a loud error, not a hang
+    if (!FIRST && ctl_s[3]) {  // never seen: the hand-off did not arrive within its wall-clock budget -> a loud error, not a hang
         if (threadIdx.x == 0) atomicAdd(&st->handoff_timeouts, 1);
         return;
     }
-    if (ctl_s[1]) return;  // the loop is finished (block-uniform)
+    if (!FIRST && ctl_s[1]) return;  // the loop is finished (block-uniform)
     // dev-only phase timestamps ("search_stats"): 4 x wall_clock64 (100 MHz) per block and iteration behind the 16 path
     // counters
     long long* stamps = nullptr;
     if (g.stamps && gx <= 1025 && vb < 1024 && iter_now < 24)
         stamps = g.stamps + 4 * ((size_t)iter_now * 1024 + vb);
     if (stamps && threadIdx.x == 0) stamps[0] = t_entry;
-    // ---- phase A, second half: one lane per query
-    if (lq < Q) {
+    // ---- phase A, second half: one lane per query (FIRST: every query searches — straight into the ball search below)
+    if (!FIRST && lq < Q) {
         float row[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) row[k] = 0.f;
@@ -1868,7 +1922,7 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
 #pragma unroll
         for (int k = 0; k < 9; ++k) rowbuf[padded_row(lq)][k] = row[k];
     }
-    __syncthreads();
+    if constexpr (!FIRST) __syncthreads();
     if (stamps && threadIdx.x == 0) {
         stamps[1] = wall_clock64() | ((long long)nmiss << 48);  // the block's miss count rides in the top bits
         if (g.dbg) {
@@ -1900,6 +1954,52 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
     };
     // (round 6) a workgroup WITHOUT a miss — nearly every one of a late launch — goes straight to the summing: the rows of its
     // hits are behind the barrier above; the phases below would cost it four dependent reads of the list's counter and a barrier
+    if constexpr (FIRST) {
+        // ---- the ball search of EVERY query, straight from the registers of phase A: the body of ball_phase below without its
+        // list (W as there: two groups of four per trip and lane with two lanes per query, BALL_W with one)
+        constexpr int W = FLPQ == 1 ? BALL_W : 2;
+        bool settled = false;
+        if (valid) {
+            float px, py, pz;
+            transform_point(pose_s, t4.x, t4.y, t4.z, px, py, pz);
+            float seed_d2 = INFINITY;
+            int seed_idx = 0x7fffffff, seed_pos = -1;
+            if (seed_sp >= 0) {
+                const float dx = cq.x - px, dy = cq.y - py, dz = cq.z - pz;
+                seed_d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+                seed_idx = seed_o;
+                seed_pos = seed_sp;
+            }
+            const float4 mp = make_float4(px, py, pz, __int_as_float(lq));
+            int4 ms = make_int4(__float_as_int(seed_d2), seed_idx, seed_pos, 0);
+            int p0, p1, p2, sp;
+            float L;
+            settled = search_ball_lane<W, FLPQ>(g, mp.x, mp.y, mp.z, seed_d2, in.ball_max, &cellstack[0][threadIdx.x], THREADS,
+                                                fsub, p0, p1, p2, L, sp, in.ball_empty != 0);
+            if (fsub == 0) {
+                if (settled) {
+                    const float4 q = g.pts[p0];
+                    const float4 nn = in.normals[p0];
+                    store_entry(lq, make_int4(pack_cache(p0, iter_now), __float_as_int(L * 0.999999f), p1, p2));
+                    row_or_wait(lq, mp, q, nn, p0);
+                } else {  // handed back: phases BF / B1 / B2 take it from the list
+                    if (sp >= 0) {  // a better seed than the one it came with: the nearest point of its own cell (exact distance)
+                        const float4 q = g.pts[sp];
+                        const float dx = q.x - mp.x, dy = q.y - mp.y, dz = q.z - mp.z;
+                        ms = make_int4(__float_as_int(fmaf(dz, dz, fmaf(dy, dy, dx * dx))), __float_as_int(q.w), sp, 0);
+                    }
+                    const int k = atomicAdd(&nmiss, 1);
+                    miss_p[k] = mp;
+                    miss_seed[k] = ms;
+                }
+            }
+        }
+        if (fsub == 0 && !settled) {  // masked, behind the end of the scan, or handed back (its row, if any, comes below)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) rowbuf[padded_row(lq)][k] = 0.f;
+        }
+        __syncthreads();
+    }
     const bool any_miss = nmiss > 0;  // block-uniform
     if (any_miss) {
     const int ball_lpq = !in.ball ? 0
@@ -1953,7 +2053,7 @@ __device__ __forceinline__ void iterate_body(GridView g, IterInputs in, RegState
     };
     // (the resident tail runs the late iterations — a handful of misses chip-wide: the whole-wave search, then the 4-lane
     // groups; the ball search and the 16-lane search are not compiled into it: their registers would be live around its loop)
-    if (!TAIL && nmiss > 0) {  // block-uniform
+    if (!TAIL && !FIRST && nmiss > 0) {  // block-uniform (FIRST: the ball search is through, the list holds what it handed back)
         if (ball_lpq == 8) ball_phase(std::integral_constant<int, 8>{});
         else if (ball_lpq == 4) ball_phase(std::integral_constant<int, 4>{});
         else if (ball_lpq == 2) ball_phase(std::integral_constant<int, 2>{});
@@ -2144,6 +2244,15 @@ __global__ __launch_bounds__(THREADS, MINW) void k_iterate_compact(GridView g, I
     const int lead_blocks = (lead.box && !TAIL) ? lead.solve : 0;
     iterate_body<THREADS, Q, STATS, TAIL, LAZY_KN, REC_BUILD>(g, in, st, ap, lead, (int)blockIdx.x < lead_blocks, (int)blockIdx.x,
                                                               lead_blocks, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// Iteration 0 of a registration of ONE sequence, the first launch it enqueues (option "first_build"; iterate_body<.., FIRST>):
+// 512 queries per workgroup with two lanes (the first "wide_until" launches) or one lane each.
+template <int MINW, int THREADS>
+__global__ __launch_bounds__(THREADS, MINW) void k_iterate_first(GridView g, IterInputs in, RegState* __restrict__ st,
+                                                                 AlignParams ap, FirstArgs fa) {
+    iterate_body<THREADS, IT_THREADS, false, false, 0, false, true>(g, in, st, ap, LeadArgs{}, false, (int)blockIdx.x, 0,
+                                                                    (int)blockIdx.x, (int)gridDim.x, fa);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -4189,7 +4298,39 @@ int launch_iterate_fused(icp_ctx* ctx, int* rows_out, int* quad_out, bool lead_m
     if (rc) return rc;
     const IterateDesc& d = fl.d;
     const dim3 grid(fl.grid);
+    // the packing launch register_begin held back ("first_build"): folded into this launch where it is iteration 0 in one of
+    // the two plain 512-query shapes (no cache, no records, no stamps, no tail, nothing to solve in front of it; the wide
+    // shape with its two lanes per query) — otherwise it runs now, in front of the generic kernel, as it always did
+    bool first = false;
+    if (ctx->first_pending) {
+        ctx->first_pending = false;
+        first = (fl.shape == SHAPE_WIDE || fl.shape == SHAPE_NARROW) && !fl.stats && !ctx->prof.enabled && !d.in.rec &&
+                !d.in.use_cache && d.in.iter == 0 && d.in.ball && tail_iters == 0 && !(lead_mode && d.lead.solve) &&
+                (fl.shape == SHAPE_NARROW || d.in.ball_lanes >= 2) && ctx->first_pack.n == d.in.n &&
+                ctx->first_pack.out == d.in.tgt;
+        if (!first) {
+            const int rc_pack = launch_pack_targets(ctx, ctx->first_pack);
+            if (rc_pack) return rc_pack;
+        }
+    }
     const int tok = prof_begin(ctx, 0, fl.iter);
+    if (first) {
+        const PackDesc& p = ctx->first_pack;
+        FirstArgs fa;
+        fa.xyz = p.xyz;
+        fa.tgt_out = p.out;
+        fa.init = p.init;
+        fa.keep_pose = p.keep_pose;
+        fa.gen = p.gen;
+        fa.box = p.box;
+        fa.hist = p.hist;
+        if (fl.shape == SHAPE_WIDE)
+            hipLaunchKernelGGL((k_iterate_first<4, 2 * IT_THREADS>), grid, dim3(2 * IT_THREADS), 0, ctx->stream, d.g, d.in, d.st,
+                               d.ap, fa);
+        else
+            hipLaunchKernelGGL((k_iterate_first<4, IT_THREADS>), grid, dim3(IT_THREADS), 0, ctx->stream, d.g, d.in, d.st, d.ap, fa);
+        ctx->first_launches += 1;
+    } else
     switch (fl.shape) {
         case SHAPE_LAZY11:
             hipLaunchKernelGGL((k_iterate_compact<2, IT_THREADS, IT_THREADS, false, false, 11>), grid, dim3(IT_THREADS), 0,

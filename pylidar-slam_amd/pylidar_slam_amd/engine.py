@@ -505,6 +505,10 @@ class IcpContext:
         """Registrations finished on per-iteration launches behind a timed-out hand-off (`icp_handoff_fallbacks`)."""
         return int(self._lib.icp_handoff_fallbacks(self._h))
 
+    def first_build_launches(self) -> int:
+        """Registrations whose first launch was the first-iteration build (`icp_first_build_launches`, option "first_build")."""
+        return int(self._lib.icp_first_build_launches(self._h))
+
     def map_points(self) -> np.ndarray:
         out = np.empty((self.map_size(), 3), np.float32)
         if out.shape[0]:

@@ -1,20 +1,30 @@
 """dev: mean per-frame GPU timeline of the odometry_loop leg from a rocprofv3 kernel trace (csv): for the frames of the
 timed pass, every kernel launch in order with its start offset from the frame's first launch, its duration and the idle
-gap in front of it."""
+gap in front of it.
+    frame_timeline.py TRACE.csv [ANCHOR] [--anchor NAME]
+A frame begins at every launch whose kernel name contains the anchor (default k_distort, as before; the headline loop of
+bench.py, which has no de-skew, used to be cut at k_pack_targets: with option "first_build" a registration has no such
+launch — cut it at k_project instead: --anchor k_project)."""
+import argparse
 import csv
-import sys
-from collections import defaultdict
 
-rows = list(csv.DictReader(open(sys.argv[1])))
-anchor = sys.argv[2] if len(sys.argv) > 2 else "k_distort"
+ap = argparse.ArgumentParser()
+ap.add_argument("trace")
+ap.add_argument("anchor_pos", nargs="?", default=None, metavar="ANCHOR")
+ap.add_argument("--anchor", default=None, help="substring of the kernel name a frame begins with")
+args = ap.parse_args()
+rows = list(csv.DictReader(open(args.trace)))
+anchor = args.anchor or args.anchor_pos or "k_distort"
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 def short(n):
     n = n.replace("void ", "").replace("icp::", "")
     return n.split("(")[0][:60]
 frames, cur = [], None
+# (an anchor that IS a kernel's name cuts at that kernel alone: "k_project" must not cut at k_project_resolve as well)
+exact = any(short(r["Kernel_Name"]) == anchor for r in rows)
 for r in rows:
     n = short(r["Kernel_Name"])
-    if anchor in n:
+    if (n == anchor) if exact else (anchor in n):
         cur = []
         frames.append(cur)
     if cur is not None:
