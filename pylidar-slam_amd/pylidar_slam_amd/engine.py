@@ -690,8 +690,9 @@ class IcpContext:
         dxs = (C.c_float * (6 * cap))()
         res = IcpRegisterResult()
         init = _pose16(init_pose if init_pose is not None else np.eye(4))
-        self._check(self._lib.icp_pmap_register(self._h, p, n, mem, TARGETS_SKIP_NULL if skip_null else TARGETS_ALL,
-                                                init, C.byref(res), losses, dxs))
+        self._check_registration(self._lib.icp_pmap_register(self._h, p, n, mem,
+                                                             TARGETS_SKIP_NULL if skip_null else TARGETS_ALL, init,
+                                                             C.byref(res), losses, dxs), res, losses, dxs)
         return self._result(res, losses, dxs)
 
     def pmap_register_launch(self, points: Array, init_pose=None, skip_null: bool = False):
