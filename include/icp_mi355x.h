@@ -550,7 +550,19 @@ int icp_register_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int 
  * t) before it has collected the pose of frame t: the GPU never idles between frames while the host still receives
  * every pose, one frame later. */
 int icp_register_launch_from_last(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode);
-int icp_iteration_accumulate(icp_ctx* ctx); /* search + normals + reduce into the 32-double device vector */
+/* search + normals + reduce into the 32-double device vector: 21 upper-triangular JtJ, 6 Jtr, sum (w r)^2, sum r^2, the
+ * count of valid rows, and two pad elements (30, 31) that are always 0.0.  A rank whose slice is empty (n = 0) or holds
+ * only masked rows (NaN; (0,0,0) under ICP_TARGETS_SKIP_NULL) writes EXACT ZEROS into elements 0 .. 29 — never what an
+ * earlier iteration or registration left there — so any cut of a scan may be registered, a world larger than the scan
+ * included, and the Invalid-Jacobian test applies to the summed system alone (a slice that is singular on its own is no
+ * error).  Elements 27 and 28 are sums of float64 products of the float32 operands on the fused path and of float32
+ * squares on the unfused and the point-to-point path (1e-8 apart).  Behind the end of the loop (the stop threshold, a
+ * guard or an error decided by icp_iteration_solve, identically on every rank) both calls return without writing: a
+ * driver may go on calling accumulate / all-reduce / solve for a fixed iteration count — the vector then holds stale
+ * sums that grow world-fold per all-reduce, which nothing reads: the result is that of the stopping iteration, and
+ * icp_register_begin starts the next registration from a vector that every accumulate overwrites
+ * (tests/test_gpu_sharded_audit.py). */
+int icp_iteration_accumulate(icp_ctx* ctx);
 int icp_iteration_solve(icp_ctx* ctx);      /* 6x6 solve + pose update from the (possibly all-reduced) vector */
 int icp_register_end(icp_ctx* ctx, icp_register_result* result, double* loss_per_iter_out, float* dx_per_iter_out);
 void* icp_normal_equations_ptr(icp_ctx* ctx); /* device pointer, 32 doubles */

@@ -52,6 +52,14 @@ def sharded_register(engine, local_points, init_pose=None, iterations: Optional[
     `engine` is an `IcpContext` (or anything with the same five calls): register_begin / iteration_accumulate /
     normal_equations_tensor / iteration_solve / register_end.  `local_points` is this rank's slice of the scan.
     Without a process group the loop degenerates to the single-GPU registration (a group of one rank still all-reduces).
+
+    Any cut is allowed: a rank whose slice is empty (`shard_bounds` leaves ranks empty whenever n < world * ceil(n /
+    world), e.g. n = 5 over 8 ranks) or holds only NaN / skipped null rows contributes exact zeros, and a slice that is
+    singular on its own is no error — the Invalid Jacobian is decided on the summed system, on every rank alike.  Every
+    rank must issue the same number of iterations: behind a stop (threshold, guard, error — the same decision on every
+    rank, from the same summed vector) accumulate and solve return at once, the all-reduce goes on summing stale vectors
+    that nothing reads, and the result is that of the stopping iteration.  Held shard by shard against float64 on one
+    GPU by tests/test_gpu_sharded_audit.py; the transport between two GPUs is not covered there.
     """
     import torch.distributed as dist
     # (a process group of ONE rank still issues its collective: that is how the 1-GPU test box exercises RCCL)

@@ -264,7 +264,8 @@ def _rank_main_exchange(rank, world, port, out):
         solo.map_set(torch.from_numpy(model).cuda())
         timed_out = timed_out and np.array_equal(alone.pose, solo.register(mine).pose)
         np.savez(out, pose=res.pose, losses=res.losses, dx=res.dx, pose2=res2.pose,
-                 all=np.stack([p.numpy() for p in poses]), targets=res.num_targets, timed_out=timed_out)
+                 all=np.stack([p.numpy() for p in poses]), targets=res.num_targets, timed_out=timed_out,
+                 iterations=res.iterations, losses2=res2.losses, dx2=res2.dx, iterations2=res2.iterations)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -273,7 +274,10 @@ def test_in_library_exchange_world_size_2_on_one_gpu(torch_cuda, tmp_path):
     """The per-iteration exchange behind the C ABI (icp_exchange_*): two processes on the one GPU map each other's
     inbox through IPC, `icp_register` on each rank enqueues iteration kernel + sum/exchange/solve kernel per iteration,
     nothing else.  Same bits on both ranks, the single-process result up to the association of the float64 sums, and a
-    peer that stays away produces ICP_ERR_EXCHANGE after the configured wait instead of a hung GPU."""
+    peer that stays away produces ICP_ERR_EXCHANGE after the configured wait instead of a hung GPU.
+    The association is the documented one: both registrations of rank 0 — pose, losses, steps, iteration count — equal
+    bit for bit the same registrations through a `sharded_audit.SimulatedWorld` of two contexts in this process, which
+    sums the two vectors in float64 in rank order (measured on an MI355X: equal, 2 x 10 iterations)."""
     import torch.multiprocessing as mp
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -301,6 +305,26 @@ def test_in_library_exchange_world_size_2_on_one_gpu(torch_cuda, tmp_path):
     assert np.array_equal(r.pose, ref.pose) and np.array_equal(r.losses, ref.losses)
     solo.exchange_destroy()
     assert np.array_equal(solo.register(scan).pose, ref.pose)
+    # the rank-order sum is the contract of k_sum_exchange_solve: the same two registrations through a simulated world of
+    # two contexts in THIS process (tests/sharded_audit.py: every rank's 32 doubles summed in float64 in rank order by
+    # torch, written back, solved by icp_iteration_solve) give rank 0's pose, losses and steps bit for bit
+    from pylidar_slam_amd.distributed import shard_bounds
+    from sharded_audit import SimulatedWorld, check_exchange_order
+    ranks = [_ctx(height=32, width=1024, max_num_alignments=10, threshold_delta_pose=0.0, scheme="geman_mcclure", sigma=0.3)
+             for _ in range(2)]
+    for c in ranks:
+        c.map_set(model)
+    shards = [np.ascontiguousarray(scan[slice(*shard_bounds(scan.shape[0], 2, r))]) for r in range(2)]
+    world = SimulatedWorld(ranks)
+    first = world.run(shards, None, 10).results[0]
+    second = world.run(shards, first[1].pose, 10).results[0]
+    RankZero = type("RankZero", (), {})
+    for (rc, res), sfx in ((first, ""), (second, "2")):
+        theirs = RankZero()
+        theirs.pose, theirs.losses, theirs.dx = got["pose" + sfx], got["losses" + sfx], got["dx" + sfx]
+        theirs.iterations = int(got["iterations" + sfx])
+        theirs.params, theirs.converged = res.params, res.converged  # (not saved by the ranks: not compared)
+        assert rc == 0 and not check_exchange_order((rc, res), (0, theirs), f"the in-library exchange, registration {sfx or 1}")
 
 
 def test_bench_gpus_2_launches_its_own_ranks(torch_cuda):
