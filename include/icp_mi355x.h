@@ -995,6 +995,16 @@ int icp_exchange_destroy(icp_ctx* ctx);
  * registrations run the fused path.  world = 1 reduces to the eager single-GPU estimation (same values). */
 int icp_map_normals_owned(icp_ctx* ctx, int32_t rank, int32_t world, float* normals_by_index);
 int icp_map_normals_install(icp_ctx* ctx, const float* normals_by_index);
+/* Test support for the normal cache (no reference counterpart): the cache of the hash grid as it stands, by ORIGINAL map
+ * index, in the layout of icp_map_normals_owned / _install.
+ *   normals4_out  [M,4] float32 (M = icp_map_size): (nx, ny, nz, 1) with the bits the cache holds where the point's normal is
+ *                 there (estimated, installed, or carried over a pose-only update by option "carry_normals"), four zeros where
+ *                 it is not — a point whose normal the next search would estimate on demand
+ * Launches nothing: nothing is estimated and no flag changes; it waits for the context's map stream and its own copies, so a
+ * map update enqueued before the call is seen complete.  Refused with ICP_ERR_INVALID_ARGUMENT while a registration or a
+ * frame is in flight or uncollected (icp_register_end / icp_frame_end first) and with ICP_ERR_EMPTY_MAP on an empty map;
+ * icp_last_error says which.  The map, the cache, the NN cache and the registration state are left as they were. */
+int icp_map_normals_peek(icp_ctx* ctx, float* normals4_out, int out_mem);
 
 /* ---- aggregated world map: one point per voxel of everything a drive has seen, kept on the device -----------------------
  * The first step of the reference's loop closure (slam/loop_closure.py:272-291: grid-sample every registered cloud, move it

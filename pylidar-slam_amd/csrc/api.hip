@@ -1607,6 +1607,39 @@ int icp_map_normals_install(icp_ctx* ctx, const float* normals_by_index) {
     return launch_normals_install(ctx, normals_by_index);
 }
 
+// Test support: the grid's normal cache as it stands, by original index.  Three copies and a permutation on the host — no
+// launch, so nothing is estimated and no flag moves (DeviceGuard has joined the map stream).
+int icp_map_normals_peek(icp_ctx* ctx, float* normals4_out, int out_mem) {
+    DeviceGuard device_guard(ctx);
+    if (!ctx || !normals4_out) return ICP_ERR_INVALID_ARGUMENT;
+    if (ctx->in_registration || ctx->result_pending() || frame_in_flight(ctx))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_map_normals_peek: registration in progress");
+    if (ctx->map_m <= 0 || !ctx->grid_valid) return fail(ctx, ICP_ERR_EMPTY_MAP, "icp_map_normals_peek: the local map is empty");
+    const size_t m = (size_t)ctx->map_m;
+    if (ctx->normals.bytes < m * sizeof(float4) || ctx->nflag.bytes < m * sizeof(int) || ctx->pos_of_orig.bytes < m * sizeof(int))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_map_normals_peek: the grid holds no normal cache");
+    std::vector<float> cache(m * 4), out(m * 4, 0.f);
+    std::vector<int> flag(m), pos(m);
+    ICP_HIP(ctx, hipMemcpyAsync(cache.data(), ctx->normals.ptr, m * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    ICP_HIP(ctx, hipMemcpyAsync(flag.data(), ctx->nflag.ptr, m * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    ICP_HIP(ctx, hipMemcpyAsync(pos.data(), ctx->pos_of_orig.ptr, m * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t o = 0; o < m; ++o) {
+        const int s = pos[o];
+        if (s < 0 || (size_t)s >= m) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_map_normals_peek: a position outside the grid");
+        if (flag[s] != 1) continue;
+        memcpy(&out[4 * o], &cache[4 * (size_t)s], 3 * sizeof(float));  // (the bits as they stand, NaN payloads included)
+        out[4 * o + 3] = 1.f;
+    }
+    if (out_mem == ICP_MEM_DEVICE) {
+        ICP_HIP(ctx, hipMemcpyAsync(normals4_out, out.data(), m * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+        ICP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        memcpy(normals4_out, out.data(), m * sizeof(float4));
+    }
+    return ICP_OK;
+}
+
 // ---- profiling ------------------------------------------------------------------------------------------------------
 int icp_profile_enable(icp_ctx* ctx, int enable) {
     DeviceGuard device_guard(ctx);

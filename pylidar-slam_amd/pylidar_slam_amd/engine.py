@@ -867,6 +867,13 @@ class IcpContext:
             raise AssertionError(f"expected [{self.map_size()}, 4] normals, got {tuple(t.shape)}")
         self._check(self._lib.icp_map_normals_install(self._h, t.data_ptr()))
 
+    def map_normals_peek(self) -> np.ndarray:
+        """The grid's normal cache as it stands (test support: `icp_map_normals_peek`): [M,4] float32 by original map index,
+        (nx, ny, nz, 1) where the normal is there and zeros where it is not.  Estimates nothing and changes no flag."""
+        out = np.zeros((self.map_size(), 4), np.float32)
+        self._check(self._lib.icp_map_normals_peek(self._h, out.ctypes.data, MEM_HOST))
+        return out
+
     # ---- multi-GPU seam ----------------------------------------------------------------------------------------------
     def normal_equations_tensor(self) -> torch.Tensor:
         """A torch-owned [32] f64 device vector installed as the context's normal-equation buffer, so that

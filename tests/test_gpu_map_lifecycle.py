@@ -18,6 +18,7 @@ model anywhere: neither the library nor the model had to be changed.
 import numpy as np
 import pytest
 
+import carry_audit as C
 import iteration_audit as A
 import map_lifecycle as L
 
@@ -122,8 +123,11 @@ def _apply_device_pose(ctx, model, op, i, state):
         ins = ctx.map_update(None, op.cloud, op.skip_null)
     else:
         rc, res = A.raw_register(ctx, scans[frame], init, True)
+        if state.get("before") is not None:
+            state["before"] = ctx.map_normals_peek()  # (the cache the update carries: behind the registration, not in front of it)
         ins = ctx.map_update(None, op.cloud, op.skip_null)
     assert rc == A.ICP_OK and res.iterations == L.K_REG, (i, rc, res.iterations)
+    state["rel"] = res.pose
     model.update(res.pose, op.cloud, op.skip_null)
     return ins
 
@@ -132,10 +136,21 @@ def _run(torch, name, entry, options=(), worst=None, normals_out=None, **kw):
     s = L.script(name)
     ctx, model = _ctx(s.local_map_size, options, **kw), L.MapModel(s.local_map_size)
     state = dict(scans=s.scans, frame=0)
-    figs = dict(share=0.0, mismatches=0, worst_tie=0.0, min_dot=1.0, ratio=0.0, searched=0, registered=0, normal_bits=0)
+    figs = dict(share=0.0, mismatches=0, worst_tie=0.0, min_dot=1.0, ratio=0.0, searched=0, registered=0, normal_bits=0,
+                carried_bits=0)
+    from pylidar_slam_amd.engine import IcpContext
     for i, op in enumerate(s.ops):
         tag = f"{name}/{entry} op {i} ({op.note or op.kind})"
+        # a pose-only update of a map with points CARRIES the normals the grid holds (unless "carry_normals" is 0): the cache
+        # read back behind it is held to the bit model of tests/carry_audit.py, applied to the cache read back in front of it
+        carried = isinstance(ctx, IcpContext) and op.kind == "update" and op.cloud is None and len(model) > 0 and \
+            ("carry_normals", 0) not in tuple(options)
+        state["before"] = ctx.map_normals_peek() if carried else None
+        state["rel"] = op.rel
         ins = _apply(torch, ctx, model, op, entry, i, state)
+        if carried:
+            fig = C.check_step(tag, state["before"], ctx.map_normals_peek(), C.transform_of(state["rel"]))
+            figs["carried_bits"] += fig["flagged"]
         L.check_state(ctx, model, tag, ins)
         figs["ratio"] = max(figs["ratio"], model.check_against_float64())
         if op.register is not None:
@@ -147,7 +162,6 @@ def _run(torch, name, entry, options=(), worst=None, normals_out=None, **kw):
             # operation with "carry_normals" 0): those are held to the bit model too; behind a pose-only update they are carried
             # (the oracle-backed context of tests/test_map_lifecycle.py estimates every time, in the reference's arithmetic: the
             # model's float64 bar instead of its bits)
-            from pylidar_slam_amd.engine import IcpContext
             library = isinstance(ctx, IcpContext)
             estimated = not library or op.cloud is not None or ("carry_normals", 0) in tuple(options)
             fig, _, normals = L.check_search(ctx, model, tag, seed=i, estimated=estimated, bits=library)
@@ -164,7 +178,8 @@ def _run(torch, name, entry, options=(), worst=None, normals_out=None, **kw):
     print(f"{name}/{entry}{' ' + str(options) if options else ''}: {len(s.ops)} operations with the model's bits; "
           f"{figs['searched']} searches, mismatch share <= {figs['share']:.2e} ({figs['mismatches']} probes at most, worst tie "
           f"{figs['worst_tie']:.1e}), min |dot| {figs['min_dot']:.7f}; {figs['registered']} registrations audited; "
-          f"float64 ratio {figs['ratio']:.3f}; {figs['normal_bits']} estimated normals bit-equal to their model")
+          f"float64 ratio {figs['ratio']:.3f}; {figs['normal_bits']} estimated and {figs['carried_bits']} carried normals bit-equal "
+          f"to their models")
     return figs
 
 
