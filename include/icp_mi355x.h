@@ -268,7 +268,9 @@ int icp_synchronize(icp_ctx* ctx);
  *                                   costs ~2 us of stream time: 40 pairs per frame are 10 % of a 0.8 ms registration)
  * The library reads no environment variables. */
 int icp_set_option(icp_ctx* ctx, const char* name, double value);
-/* runtime re-configuration of the alignment (RIGID_ALIGNMENT.load, slam/odometry/alignment.py:200-208) */
+/* runtime re-configuration of the alignment (RIGID_ALIGNMENT.load, slam/odometry/alignment.py:200-208).  Like icp_set_option and
+ * icp_set_cost: iterations a chunked launch holds back are enqueued first, and the call is refused ("registration in
+ * progress") between icp_register_begin and icp_register_end (a longer loop would re-allocate the state the iterations run on) */
 int icp_set_alignment(icp_ctx* ctx, int32_t scheme, float sigma, int32_t max_num_alignments,
                       float threshold_delta_pose);
 /* the alignment mode of the registration loop (icp_cost; default point to plane) */
@@ -375,7 +377,10 @@ int icp_estimate_timestamps(icp_ctx* ctx, const float* rows, int64_t n, int stri
 int icp_kitti360_prepare(icp_ctx* ctx, const float* scan, int64_t n, int stride, int mem, int clockwise, double phi_0,
                          double* xyz_out, double* timestamps_out, int out_mem);
 
-/* ---- local map: KdTreeLocalMap (slam/odometry/local_map.py:254-427) ---------------------------------------------- */
+/* ---- local map: KdTreeLocalMap (slam/odometry/local_map.py:254-427) ----------------------------------------------
+ * Every call that changes the map (icp_map_init, icp_map_set, the icp_map_update family) first enqueues the iterations a
+ * chunked launch holds back, and is refused ("registration in progress") between icp_register_begin and icp_register_end: the
+ * caller's next icp_iteration_accumulate would search a grid that is gone or rebuilt. */
 int icp_map_init(icp_ctx* ctx);                                             /* init()               :279-288 */
 int icp_map_set(icp_ctx* ctx, const float* xyz, int64_t m, int mem);        /* set_map_pointcloud() :289-299 */
 /* update() :302-362 — move the map by inv(rel), append `new_xyz` (rows with NaN dropped; NULL / n = 0: pose-only
@@ -394,7 +399,9 @@ int icp_map_update(icp_ctx* ctx, const float rel_pose[16], const float* new_xyz,
  * host without waiting for it; icp_map_update_staged then performs update() :302-362 with those rows — same map, same
  * *inserted_out — and has nothing to wait for when anything that synchronises (icp_register_end) ran in between: one host
  * round trip per frame less than icp_map_update with a cloud.  A staged cloud is consumed by the first
- * icp_map_update_staged and replaced by the next icp_map_stage_cloud; rel_pose = NULL as for icp_map_update. */
+ * icp_map_update_staged and replaced by the next icp_map_stage_cloud; rel_pose = NULL as for icp_map_update.  Both are refused
+ * ("a frame is launched and awaits its end") between icp_frame_launch and icp_frame_end (or the projective pair): the staged rows
+ * are then the frame's, which a key frame's end inserts. */
 int icp_map_stage_cloud(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int row_mode);
 int icp_map_update_staged(icp_ctx* ctx, const float rel_pose[16], int64_t* inserted_out);
 /* update(new_vertex_map=...) :320-324 — appends the pixels of a [3,H,W] vertex map with norm > 0.01 */
@@ -471,6 +478,8 @@ int icp_compute_normal_map(icp_ctx* ctx, const float* vmap, int mem, int kernel_
  * ref_fields [k_maps,c_fields,H,W] along.  neighbors_out [3,H,W], fields_out [c_fields,H,W]. */
 int icp_compute_neighbors(icp_ctx* ctx, const float* tgt_vmap, const float* ref_vmaps, const float* ref_fields,
                           int k_maps, int c_fields, int mem, float* neighbors_out, float* fields_out, int out_mem);
+/* icp_pmap_init and icp_pmap_update are refused ("a frame is launched and awaits its end") between the two frame calls of the
+ * context: the window is the one the frame registers against and its end re-expresses and appends to. */
 int icp_pmap_init(icp_ctx* ctx); /* init() :113-119 */
 /* update() :122-174 — re-express the kept maps by inv(rel_pose), append `vmap` [3,H,W] with its normal map (NULL:
  * pose-only update), drop the oldest beyond local_map_size, rebuild the model (build_model :177-202). */
@@ -483,7 +492,8 @@ int icp_pmap_get_model(icp_ctx* ctx, float* model_v4_out, float* model_n4_out, i
 int icp_pmap_nearest_neighbor_search(icp_ctx* ctx, const float* xyz, int64_t n, int mem, float* rows9_out,
                                      int64_t* count_out, int out_mem);
 /* register_new_frame (slam/odometry/icp_odometry.py:248-299) against the projective map; same contract as
- * icp_register. */
+ * icp_register.  Refused (ICP_ERR_INVALID_ARGUMENT) while a registration of the context is in progress or a launched one
+ * awaits icp_register_end: the call collects through the result slots, oldest first, and would hand out that older result. */
 int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16],
                       icp_register_result* result, double* loss_per_iter_out, float* dx_per_iter_out);
 
@@ -537,11 +547,34 @@ int icp_register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int t
  * ICPFrameToModel.__update_map, icp_odometry.py:379) overlaps the host's wait in icp_register_end, which then blocks on
  * the registration only.  With threshold_delta_pose > 0 only a first chunk of iterations is on the stream when this
  * returns ("chunked_launch": as many as the last registration ran, plus one; launches behind an early stop are
- * device-side no-ops); icp_register_end enqueues more while the loop is still running.  Every entry point that changes
- * what those held-back iterations would see — any icp_map_update / icp_map_update_staged / icp_map_stage_cloud / icp_map_set / icp_map_init / icp_map_update_vertex_map,
- * icp_set_option / icp_set_cost / icp_set_alignment / icp_set_stream, icp_map_normals_owned / _install, icp_pmap_register,
- * the next icp_register_launch — first enqueues ALL of them, so the stream order is the call order, as if every iteration
- * had been enqueued here. */
+ * device-side no-ops); icp_register_end enqueues more while the loop is still running.
+ * CALLS BEFORE icp_register_end.  Every entry point of this header belongs to one class while a launched registration is
+ * enqueued or uncollected (tests/inflight_audit.py holds the class of each, state by state, and tests/test_gpu_inflight_audit.py
+ * holds the library to it):
+ *   ORDERED (enqueues them first): icp_map_update, icp_map_update_staged, icp_map_stage_cloud, icp_map_set, icp_map_init,
+ *       icp_map_update_vertex_map, icp_set_option, icp_set_cost, icp_set_alignment, icp_set_stream,
+ *       icp_set_normal_equations_buffer, icp_map_normals_owned / _install, icp_odometry_init, icp_register_launch,
+ *       icp_register_launch_from_last.
+ *     Each changes what the held-back iterations would see, so it first enqueues ALL of them: the stream order is the call
+ *     order, as if every iteration had been enqueued here, and the call takes effect behind the registration.  (A third
+ *     launch is refused: two results may be pending.)  The batched forms do the same for every member.
+ *   REFUSED (while a registration is enqueued or uncollected): icp_register, icp_register_begin, icp_pmap_register,
+ *       icp_pmap_register_launch, icp_nearest_neighbor_search, icp_knn_query, icp_last_neighbors, icp_last_cache_entries,
+ *       icp_align_point_to_plane, icp_align_point_to_point, icp_weighted_procrustes, icp_estimate_timestamps,
+ *       icp_kitti360_prepare, icp_map_normals_peek, icp_exchange_create / _connect / _destroy, icp_iteration_accumulate,
+ *       icp_iteration_solve, icp_frame_launch, icp_frame_end, icp_pmap_odometry_init, icp_pmap_frame_launch, icp_pmap_frame_end.
+ *     ICP_ERR_INVALID_ARGUMENT, icp_last_error names the reason, nothing changed.  They share the targets, the partial rows, the
+ *     normal equations, the state or the staging scratch with the registration, or need its result slot (icp_knn_query
+ *     enqueues the held-back iterations before it refuses).
+ *   INDEPENDENT: everything else that launches work — the projection, the grid samples, icp_voxel_hash / _statistics,
+ *     icp_distort, icp_kitti_correct_scan, icp_compact_targets, icp_compute_normal_map, icp_compute_neighbors, the projective
+ *     map (icp_pmap_init, icp_pmap_update, icp_pmap_get_model, icp_pmap_nearest_neighbor_search), icp_map_get, icp_synchronize,
+ *     the profile, aggregated maps, elevation images, refiners.  They stage through buffers no iteration reads (an iteration
+ *     reads the packed targets, the grid, the normals, the NN cache, the state, the partial rows and the mailbox) and run in
+ *     stream order behind what is enqueued; held-back iterations stay held back.
+ *   COLLECTS: icp_register_end (the oldest result first).
+ * Between icp_register_begin and icp_register_end only icp_iteration_accumulate / _solve, icp_set_stream,
+ * icp_set_normal_equations_buffer and the INDEPENDENT calls are accepted (the padded grid samples are refused there too). */
 int icp_register_launch(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_mode, const float init_pose[16]);
 /* the same with the initial guess = the pose of the previous registration on this context, READ ON THE DEVICE: the
  * constant-velocity initialisation (`ConstantVelocityInitialization`, slam/initialization.py:103-119 — the last relative
@@ -564,9 +597,13 @@ int icp_register_launch_from_last(icp_ctx* ctx, const float* xyz, int64_t n, int
  * (tests/test_gpu_sharded_audit.py). */
 int icp_iteration_accumulate(icp_ctx* ctx);
 int icp_iteration_solve(icp_ctx* ctx);      /* 6x6 solve + pose update from the (possibly all-reduced) vector */
+/* collects the registration in progress, or the OLDEST launched one.  Refused with a message: nothing to collect; a batch that
+ * still holds iterations of this context back (icp_batch_register_end collects it); a frame launched on the context, by itself
+ * or by a batch ("a frame is launched and awaits its end": icp_frame_end / icp_pmap_frame_end / the batch's end collect it). */
 int icp_register_end(icp_ctx* ctx, icp_register_result* result, double* loss_per_iter_out, float* dx_per_iter_out);
 void* icp_normal_equations_ptr(icp_ctx* ctx); /* device pointer, 32 doubles */
-/* use caller-owned device memory (e.g. a torch tensor RCCL can reduce in place) for the 32-double vector */
+/* use caller-owned device memory (e.g. a torch tensor RCCL can reduce in place) for the 32-double vector; iterations a chunked
+ * launch holds back are enqueued first (they sum into the vector they were launched with) */
 int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
 
 /* ---- one call per odometry frame: ICPFrameToModel.do_process_next_frame (slam/odometry/icp_odometry.py:157-246) ------
@@ -618,8 +655,15 @@ int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr);
  *                      loss_per_iter_out / dx_per_iter_out as for icp_register_end.
  * ICP_ERR_INVALID_ARGUMENT with a message, the context usable as before: a context that holds a projective map, an exchange or
  * profiling switched on, a context held by a batch, icp_frame_launch before icp_odometry_init or while a frame awaits its
- * icp_frame_end, icp_frame_end with nothing launched.  Single-context entry points between the two calls follow the rules of
- * icp_register_launch.  One frame at a time per context; B contexts step together through icp_batch_frame_launch /
+ * icp_frame_end, icp_frame_end with nothing launched.
+ * CALLS BETWEEN icp_frame_launch AND icp_frame_end (and between icp_pmap_frame_launch and icp_pmap_frame_end) follow the
+ * classes of icp_register_launch, with the frame's own registration, staged rows and window taken out of the caller's reach:
+ * icp_register_end, icp_map_stage_cloud, icp_map_update_staged, icp_pmap_init and icp_pmap_update are REFUSED there ("a frame
+ * is launched and awaits its end": they would collect the frame's result, replace or consume the rows a key frame inserts,
+ * or move the window its end appends to), icp_frame_end / icp_pmap_frame_end COLLECT, and icp_odometry_init /
+ * icp_pmap_odometry_init collect and drop the frame.  The ORDERED calls stay ORDERED — an explicit icp_map_update,
+ * icp_set_option, icp_set_alignment take effect behind the frame's registration and in front of the update its end enqueues.
+ * One frame at a time per context; B contexts step together through icp_batch_frame_launch /
  * icp_batch_frame_end below. */
 typedef struct icp_frame_config {
     double voxel_size;         /* > 0: GridSample (slam/preprocessing.py:207-226) in front of the frame; <= 0: the rows as given */
@@ -845,7 +889,13 @@ int icp_batch_stage(icp_batch* batch, const float* const* xyz, const int64_t* n,
  * a frame of its own; non-skipped members that differ in voxel_size or targets (one batched preprocessing and one target
  * mode per step); members on different streams.  A refusal's message ends in "(nothing was changed)"; every other status of
  * icp_batch_frame_end comes back behind a completed step.  A frame the batch has launched is ended by the batch: icp_frame_end and
- * icp_odometry_init on such a member are refused until then. */
+ * icp_odometry_init on such a member are refused until then, and so are the single calls a member refuses between its own frame
+ * calls (icp_register_end, icp_map_stage_cloud, icp_map_update_staged).
+ * MEMBERS WITH WORK OF THEIR OWN: icp_batch_stage, icp_batch_map_update, icp_batch_map_update_staged, icp_batch_pmap_update,
+ * icp_batch_pmap_register_launch and icp_batch_register_end are refused, before any member changes, while a member has launched
+ * a frame of its OWN ("a frame is launched and awaits its end": the member's end collects that registration and inserts those
+ * rows); icp_batch_register_launch, icp_batch_map_update and icp_batch_map_update_staged also while a member is between
+ * icp_register_begin and icp_register_end ("registration in progress"). */
 typedef struct icp_batch_frame {
     const float* xyz;          /* [n,3] float32, host or device (the call's `mem`) */
     int64_t n;
@@ -976,6 +1026,8 @@ int icp_batch_pmap_frame_end(icp_batch* batch, icp_frame_result* results, float*
  *   icp_exchange_connect opens the `world` handles (rank order; the own entry is ignored) and switches the context to
  *                        exchange mode; every rank must then issue the same sequence of registrations;
  *   icp_exchange_destroy leaves exchange mode and releases the mappings.
+ * All three are refused ("registration in progress") while a registration is in progress, enqueued or uncollected: its
+ * iterations were planned with or without the exchange.
  * A peer that does not deliver within the budget (option "exchange_timeout_ms", default 5000) ends the registration
  * with ICP_ERR_EXCHANGE instead of hanging the GPU — and the context LEAVES exchange mode: the ranks' sequence counters
  * and inbox tags may have diverged, so registrations fall back to the rank-local solve until every rank has called

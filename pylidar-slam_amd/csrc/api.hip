@@ -463,6 +463,8 @@ int icp_set_alignment(icp_ctx* ctx, int32_t scheme, float sigma, int32_t max_num
     ICP_HELD_FIRST(ctx);
     if (scheme < 0 || scheme > ICP_SCHEME_CAUCHY || max_num_alignments < 1)
         return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "bad alignment parameters");
+    // (between icp_register_begin and icp_register_end a longer loop would re-allocate the state the iterations run on)
+    if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     ctx->cfg.scheme = scheme;
     ctx->cfg.sigma = sigma;
     ctx->cfg.max_num_alignments = max_num_alignments;
@@ -696,6 +698,13 @@ bool frame_in_flight(const icp_ctx* ctx) {
     return (ctx->frame && ctx->frame->seq.launched) || (ctx->pframe && ctx->pframe->seq.launched);
 }
 
+// ... launched by the context ITSELF (icp_frame_launch / icp_pmap_frame_launch), not as a step of a batch: what the batched
+// forms refuse to stage over, update under or collect (the frame steps of a batch run them on members whose frame is theirs)
+bool own_frame_in_flight(const icp_ctx* ctx) {
+    return (ctx->frame && ctx->frame->seq.launched && !ctx->frame->seq.batched) ||
+           (ctx->pframe && ctx->pframe->seq.launched && !ctx->pframe->seq.batched);
+}
+
 // What icp_estimate_timestamps / icp_kitti360_prepare refuse.  They stage into scratch a registration and a frame use (the
 // staging buffers, the scan buffers of the de-skew): refused while one is enqueued or uncollected, as the alignment seams are.
 static int timestamps_refusals(icp_ctx* ctx, const char* who, int64_t n, int stride, int mem, int out_mem) {
@@ -747,9 +756,12 @@ int icp_kitti360_prepare(icp_ctx* ctx, const float* scan, int64_t n, int stride,
 }
 
 // ---- local map ------------------------------------------------------------------------------------------------------
+// (the map calls between icp_register_begin and icp_register_end: the caller's next icp_iteration_accumulate would search a
+// grid that is gone or rebuilt, with the NN cache of the old one — refused, as icp_set_option and icp_map_stage_cloud are)
 int icp_map_init(icp_ctx* ctx) {
     DeviceGuard device_guard(ctx);
     if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     ICP_HELD_FIRST(ctx);
     ctx->map_m = 0;
     ctx->cloud_sizes.clear();
@@ -761,6 +773,7 @@ int icp_map_init(icp_ctx* ctx) {
 int icp_map_set(icp_ctx* ctx, const float* xyz, int64_t m, int mem) {
     DeviceGuard device_guard(ctx);
     if (!ctx || m < 0 || (m > 0 && !xyz)) return ICP_ERR_INVALID_ARGUMENT;
+    if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     ICP_HELD_FIRST(ctx);
     icp_map_init(ctx);  // set_map_pointcloud() calls init(): `_local_map_num_elements` stays empty (local_map.py:294)
     DeviceBuffer& dst = ctx->map_xyz[ctx->map_cur];
@@ -913,6 +926,7 @@ int icp_map_update(icp_ctx* ctx, const float rel_pose[16], const float* new_xyz,
                    int64_t* inserted_out) {
     DeviceGuard device_guard(ctx);
     if (!ctx || n < 0) return ICP_ERR_INVALID_ARGUMENT;
+    if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     if (!rel_pose && !ctx->have_device_pose)
         return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "rel_pose = NULL needs a previous registration on this context");
     const bool has_cloud = new_xyz != nullptr;
@@ -942,6 +956,9 @@ int icp_map_stage_cloud(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int 
     DeviceGuard device_guard(ctx);
     if (!ctx || n < 0 || (n > 0 && !xyz)) return ICP_ERR_INVALID_ARGUMENT;
     if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
+    // (the rows a launched frame staged are the ones its end inserts for a key frame: they are not the caller's to replace)
+    if (frame_in_flight(ctx))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_map_stage_cloud: a frame is launched and awaits its end");
     ICP_HELD_FIRST(ctx);
     int rc = ensure_state(ctx);
     if (rc) return rc;
@@ -972,6 +989,10 @@ int icp_map_stage_cloud(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int 
 int icp_map_update_staged(icp_ctx* ctx, const float rel_pose[16], int64_t* inserted_out) {
     DeviceGuard device_guard(ctx);
     if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    // (... nor the caller's to consume: the end of a key frame would find no staged cloud behind its collected registration)
+    if (frame_in_flight(ctx))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_map_update_staged: a frame is launched and awaits its end");
+    if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     if (ctx->staged_rows < 0) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "no staged cloud (icp_map_stage_cloud)");
     if (!rel_pose && !ctx->have_device_pose)
         return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "rel_pose = NULL needs a previous registration on this context");
@@ -999,6 +1020,7 @@ int icp_map_update_vertex_map(icp_ctx* ctx, const float rel_pose[16], const floa
                               int64_t* inserted_out) {
     DeviceGuard device_guard(ctx);
     if (!ctx || !rel_pose || !vmap) return ICP_ERR_INVALID_ARGUMENT;
+    if (ctx->in_registration) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     ICP_HELD_FIRST(ctx);
     const int npix = ctx->cfg.height * ctx->cfg.width;
     const void* in;
@@ -1197,6 +1219,8 @@ int icp_compute_neighbors(icp_ctx* ctx, const float* tgt_vmap, const float* ref_
 int icp_pmap_init(icp_ctx* ctx) {
     DeviceGuard device_guard(ctx);
     if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    // (the window a launched frame registers against is the one its end re-expresses and appends to)
+    if (frame_in_flight(ctx)) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_pmap_init: a frame is launched and awaits its end");
     ctx->pm_slots.clear();
     ctx->pm_poses.clear();
     return ICP_OK;
@@ -1271,6 +1295,7 @@ void pmap_window_step(icp_ctx* ctx, const float rel_pose[16], int slot) {
 int icp_pmap_update(icp_ctx* ctx, const float rel_pose[16], const float* vmap, int mem, int normals_kernel_size) {
     DeviceGuard device_guard(ctx);
     if (!ctx || !rel_pose) return ICP_ERR_INVALID_ARGUMENT;
+    if (frame_in_flight(ctx)) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_pmap_update: a frame is launched and awaits its end");
     if (vmap && (normals_kernel_size < 1 || normals_kernel_size > 15 || !(normals_kernel_size & 1)))
         return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "normals_kernel_size must be odd, 1..15");
     int rc = ensure_state(ctx);
@@ -1516,6 +1541,7 @@ void* icp_normal_equations_ptr(icp_ctx* ctx) {
 int icp_set_normal_equations_buffer(icp_ctx* ctx, void* device_ptr) {
     DeviceGuard device_guard(ctx);
     if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    ICP_HELD_FIRST(ctx);  // (iterations a chunked launch holds back sum into the vector they were launched with)
     int rc = ensure_state(ctx);
     if (rc) return rc;
     ctx->neq = device_ptr ? (double*)device_ptr : ctx->neq_own.as<double>();
@@ -1563,6 +1589,8 @@ int icp_exchange_create(icp_ctx* ctx, int32_t rank, int32_t world, void* handle_
 int icp_exchange_connect(icp_ctx* ctx, const void* handles) {
     DeviceGuard device_guard(ctx);
     if (!ctx || !handles) return ICP_ERR_INVALID_ARGUMENT;
+    // (as icp_exchange_create / _destroy: iterations held back or enqueued were planned without the exchange)
+    if (ctx->in_registration || ctx->result_pending()) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "registration in progress");
     if (!ctx->x_inbox) return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_exchange_create first");
     const int world = ctx->xview.world, rank = ctx->xview.rank;
     for (int r = 0; r < world; ++r) {

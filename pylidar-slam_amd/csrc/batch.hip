@@ -265,6 +265,22 @@ static int batch_shared_options_check(icp_batch* b, const char* what) {
     return ICP_OK;
 }
 
+// What the batched map calls, the staging and the collection refuse before any member changes: a member between
+// icp_register_begin and icp_register_end (`begun`: its caller drives the iterations — a batched launch that failed on it would
+// abandon that registration, an update would rebuild the grid under it), and a member whose OWN frame is launched (its
+// icp_frame_end / icp_pmap_frame_end collects that registration, inserts those staged rows, appends to that window).
+static int batch_members_free(icp_batch* b, const char* what, bool begun, bool own_frame) {
+    for (size_t i = 0; i < b->members.size(); ++i) {
+        const icp_ctx* ctx = b->members[i];
+        const std::string who = std::string(what) + ", member " + std::to_string(i) + ": ";
+        if (begun && ctx->in_registration && !b->run_active)
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "registration in progress (nothing was changed)");
+        if (own_frame && own_frame_in_flight(ctx))
+            return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "a frame is launched and awaits its end (nothing was changed)");
+    }
+    return ICP_OK;
+}
+
 int icp_batch_register_launch(icp_batch* b, const float* const* xyz, const int64_t* n, int mem, int target_mode,
                               const float* init_poses, int from_last) {
     if (!b || !xyz || !n) return ICP_ERR_INVALID_ARGUMENT;
@@ -286,6 +302,7 @@ int icp_batch_register_launch(icp_batch* b, const float* const* xyz, const int64
                                                           "profiling or search statistics only");
     }
     if (int rc_options = batch_shared_options_check(b, "batched registration")) return rc_options;
+    if (int rc_free = batch_members_free(b, "batched registration", true, false)) return rc_free;
     BatchUnwind unwind{b, true};  // (register_begin counts the members among the registering contexts)
     int rc = ICP_OK;
     if ((rc = batch_flush(b))) return rc;  // (iterations of the previous batched registration still held back go first)
@@ -458,7 +475,7 @@ int icp_batch_stage(icp_batch* b, const float* const* xyz, const int64_t* n, int
         if (n[i] < 0 || (n[i] > 0 && !xyz[i]))
             return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched staging, member " + std::to_string(i) + ": a device cloud is required");
     int rc = front_batch_check(b, "batched staging", true);
-    if (rc || (rc = front_batch_flush(b))) return rc;
+    if (rc || (rc = batch_members_free(b, "batched staging", false, true)) || (rc = front_batch_flush(b))) return rc;
     int* mapped[ICP_BATCH_MAX_SEQUENCES] = {};
     float* out[ICP_BATCH_MAX_SEQUENCES] = {};
     for (int i = 0; i < count; ++i) {  // (as icp_map_stage_cloud, member by member)
@@ -514,6 +531,7 @@ int icp_batch_map_update(icp_batch* b) {
     DeviceGuard device_guard(b->device);
     const int count = (int)b->members.size();
     icp_ctx* first = b->members[0];
+    if (int rc_free = batch_members_free(b, "batched map update", true, true)) return rc_free;
     {   // the pose-only update reads the END of the registration: iterations the batch still holds back go first
         const int rc_flush = batch_flush(b);
         if (rc_flush) return rc_flush;
@@ -568,6 +586,7 @@ int icp_batch_map_update_staged(icp_batch* b, const float* rel_poses, const int3
     icp_ctx* const* ctxs = b->members.data();
     icp_ctx* first = ctxs[0];
     // ---- every member is checked before any member changes (window, map, jobs, grid): a refused call changes nothing
+    if (int rc_free = batch_members_free(b, "batched map update", true, true)) return rc_free;
     for (int i = 0; i < count; ++i) {
         icp_ctx* ctx = ctxs[i];
         { DeviceGuard join_map_stream(ctx); }
@@ -698,7 +717,7 @@ static int pmap_batch_check(icp_batch* b, const char* what) {
         if (ctx->batch_hold || ctx->launch_remaining > 0)
             return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, who + "kd-tree iterations are still held back: collect them first");
     }
-    return ICP_OK;
+    return batch_members_free(b, what, false, true);  // (frame 0 of a member's own frame call: launched, nothing pending)
 }
 
 int icp_batch_pmap_register_launch(icp_batch* b, const float* const* xyz, const int64_t* n, int mem, int target_mode,
@@ -860,6 +879,8 @@ int icp_batch_pmap_update(icp_batch* b, const float* rel_poses, const float* con
 int icp_batch_register_end(icp_batch* b, icp_register_result* results, double* loss_per_iter_out, float* dx_per_iter_out) {
     if (!b || !results) return ICP_ERR_INVALID_ARGUMENT;
     DeviceGuard device_guard(b->device);
+    // (a member's own frame: its icp_frame_end collects that registration — collected here, the frame could never end)
+    if (int rc_free = batch_members_free(b, "icp_batch_register_end", false, true)) return rc_free;
     // a registration enqueued in chunks: wait for what is on the stream; while a member is still running and iterations are
     // held back, the next chunk (four iterations), and look again
     while (b->run_active) {
@@ -888,7 +909,7 @@ int icp_batch_register_end(icp_batch* b, icp_register_result* results, double* l
     const size_t cap = (size_t)b->members[0]->cfg.max_num_alignments;
     for (size_t i = 0; i < b->members.size(); ++i) {
         icp_ctx* ctx = b->members[i];
-        const int rc = icp_register_end(ctx, &results[i], loss_per_iter_out ? loss_per_iter_out + i * cap : nullptr,
+        const int rc = register_collect(ctx, &results[i], loss_per_iter_out ? loss_per_iter_out + i * cap : nullptr,
                                         dx_per_iter_out ? dx_per_iter_out + i * cap * 6 : nullptr);
         if (rc) results[i].status = rc;  // (whatever ended this member: a caller tells the healthy members by their status)
         if (rc && !first_rc) {

@@ -35,7 +35,7 @@ void frame_drop_pending(icp_ctx* ctx, icp_frame_seq* s, icp_frame_io* io) {
     if (!s->launched) return;
     if (s->registered && ctx->result_pending()) {
         icp_register_result r;
-        (void)icp_register_end(ctx, &r, nullptr, nullptr);
+        (void)register_collect(ctx, &r, nullptr, nullptr);
     }
     if (io->copy_started) (void)hipEventSynchronize(io->copy_done);
     io->copy_started = false;
@@ -56,7 +56,7 @@ int frame_end_first(icp_ctx* ctx, icp_frame_seq* s, const icp_frame_io* io, int6
 
 int frame_collect(icp_ctx* ctx, icp_frame_seq* s, icp_frame_io* io, icp_frame_result* result, double* loss_per_iter_out,
                   float* dx_per_iter_out) {
-    const int rc = icp_register_end(ctx, &result->reg, loss_per_iter_out, dx_per_iter_out);
+    const int rc = register_collect(ctx, &result->reg, loss_per_iter_out, dx_per_iter_out);
     if (io->copy_started) ICP_HIP(ctx, hipEventSynchronize(io->copy_done));
     result->samples = s->sampled && io->copy_started ? (int64_t)*io->pin_count : s->n;
     if (rc) {

@@ -919,6 +919,7 @@ int ensure_state(icp_ctx* ctx);
 int prepare_targets_and_state(icp_ctx* ctx, int64_t n, const float* init_pose, bool keep_pose = false,
                               icp::PackDesc* defer = nullptr);
 bool frame_in_flight(const icp_ctx* ctx);
+bool own_frame_in_flight(const icp_ctx* ctx);  // ... by the context itself, not as a step of a batch
 int map_update_impl(icp_ctx* ctx, const float rel_pose[16], const float* new_dev, const int* flags_dev, int64_t n,
                     bool has_cloud, int64_t* inserted_out, int64_t known_count = -1);
 int map_update_body(icp_ctx* ctx, const float rel_pose[16], const float* new_dev, const int* flags_dev, int64_t n,
@@ -939,6 +940,8 @@ int result_fold_begin(icp_ctx* ctx, bool refresh);
 int result_hand_over(icp_ctx* ctx, int rc, int enqueued, int remaining, bool refresh = false,
                      hipEvent_t shared_event = nullptr);
 int continue_launch(icp_ctx* ctx, int count);
+// icp_register_end behind its refusal of a context whose frame is launched: what the frame calls and the batch collect with
+int register_collect(icp_ctx* ctx, icp_register_result* result, double* loss_per_iter_out, float* dx_per_iter_out);
 // search_stats.hip: the "search_stats" dump of a collected registration to stderr (nothing unless the option is on)
 void search_stats_report(icp_ctx* ctx, const icp::RegState& st);
 

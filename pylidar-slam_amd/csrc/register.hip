@@ -44,7 +44,12 @@ int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int ta
                       icp_register_result* result, double* loss_per_iter_out, float* dx_per_iter_out) {
     DeviceGuard device_guard(ctx);
     if (!ctx || !result || n < 0 || (n > 0 && !xyz)) return ICP_ERR_INVALID_ARGUMENT;
-    ICP_HELD_FIRST(ctx);
+    // (icp_register_end below hands out the OLDEST pending result: with one pending it would return that registration as this
+    // one's and leave this one uncollected, the context "in registration" for good)
+    if (ctx->in_registration || ctx->result_pending())
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_pmap_register: a registration of this context is in progress or awaits "
+                                                   "icp_register_end");
+    ICP_HELD_FIRST(ctx);  // (a batch that holds iterations back is refused here)
     if (ctx->pm_slots.empty()) return fail(ctx, ICP_ERR_EMPTY_MAP, "the local map is empty");
     int rc = pmap_register_begin(ctx, xyz, n, mem, target_mode, init_pose, false, nullptr, true);
     if (rc) return rc;
@@ -64,7 +69,7 @@ int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int ta
             if (done) break;
         }
     }
-    return icp_register_end(ctx, result, loss_per_iter_out, dx_per_iter_out);
+    return register_collect(ctx, result, loss_per_iter_out, dx_per_iter_out);
 }
 
 // ---- registration ---------------------------------------------------------------------------------------------------
@@ -159,7 +164,9 @@ bool fused_path(const icp_ctx* ctx) {
 
 int icp_iteration_accumulate(icp_ctx* ctx) {
     DeviceGuard device_guard(ctx);
-    if (!ctx || !ctx->in_registration) return ICP_ERR_INVALID_ARGUMENT;
+    if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    if (!ctx->in_registration)
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_iteration_accumulate: no registration in progress (icp_register_begin first)");
     int rc;
     if (fused_path(ctx)) {
         int rows = 0, quad = 1;
@@ -175,7 +182,9 @@ int icp_iteration_accumulate(icp_ctx* ctx) {
 
 int icp_iteration_solve(icp_ctx* ctx) {
     DeviceGuard device_guard(ctx);
-    if (!ctx || !ctx->in_registration) return ICP_ERR_INVALID_ARGUMENT;
+    if (!ctx) return ICP_ERR_INVALID_ARGUMENT;
+    if (!ctx->in_registration)
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_iteration_solve: no registration in progress (icp_register_begin first)");
     return launch_solve(ctx);
 }
 
@@ -311,9 +320,20 @@ static int recover_handoff(icp_ctx* ctx, RegState& st, std::vector<char>& block)
     return ICP_OK;
 }
 
+// A frame call owns the registration it launched: icp_frame_end / icp_pmap_frame_end (or the batch's) collect it, read the
+// key-frame test off its pose and insert the staged rows.  Collected from outside, the frame could neither end nor be launched
+// again (its end fails in frame_collect and leaves the frame launched).  The library's own collectors call register_collect.
 int icp_register_end(icp_ctx* ctx, icp_register_result* result, double* loss_per_iter_out, float* dx_per_iter_out) {
+    if (ctx && result && frame_in_flight(ctx))
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_register_end: a frame is launched and awaits its end");
+    return register_collect(ctx, result, loss_per_iter_out, dx_per_iter_out);
+}
+
+int register_collect(icp_ctx* ctx, icp_register_result* result, double* loss_per_iter_out, float* dx_per_iter_out) {
     DeviceGuard device_guard(ctx, false);  // (the pose arrives while the map update runs)
-    if (!ctx || !result || (!ctx->in_registration && !ctx->result_pending())) return ICP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !result) return ICP_ERR_INVALID_ARGUMENT;
+    if (!ctx->in_registration && !ctx->result_pending())
+        return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "icp_register_end: no registration to collect");
     if (ctx->batch_hold)
         return fail(ctx, ICP_ERR_INVALID_ARGUMENT, "a batched registration of this context still holds iterations back: "
                                                    "collect it with icp_batch_register_end");
@@ -512,7 +532,7 @@ int icp_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int target_
     int rc = icp_register_begin(ctx, xyz, n, mem, target_mode, init_pose);
     if (rc) return rc;
     if ((rc = enqueue_iterations(ctx, true))) return rc;
-    return icp_register_end(ctx, result, loss_per_iter_out, dx_per_iter_out);
+    return register_collect(ctx, result, loss_per_iter_out, dx_per_iter_out);
 }
 
 // icp_pmap_register, enqueued: begin + every iteration on the stream, the result block delivered to its pinned slot behind the
