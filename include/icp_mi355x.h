@@ -416,6 +416,13 @@ int icp_handoff_fallbacks(const icp_ctx* ctx);
 /* registrations of this context whose first launch was the first-iteration build (option "first_build") instead of the packing
  * launch + the generic kernel (diagnostics; no reference counterpart) */
 int icp_first_build_launches(const icp_ctx* ctx);
+/* registrations of this context whose launches were latched onto lead launches when they began (icp_register_begin and what
+ * builds on it, icp_batch_register_launch): no other context of the process was registering on the device at that moment.  One
+ * finished by the recovery behind a timed-out hand-off stays counted (diagnostics; no reference counterpart) */
+int icp_lead_registrations(const icp_ctx* ctx);
+/* contexts of this process that are in a registration against the kd-tree style map, or hold an uncollected result of one, on
+ * `device` right now: what the decision above looks at.  -1 outside 0..63 (diagnostics; no reference counterpart) */
+int icp_registering_contexts(int device);
 int icp_map_get(icp_ctx* ctx, float* xyz_out, int out_mem); /* current map [M,3] in insertion order */
 /* nearest_neighbor_search() :372-395 + __get_normals :397-422 — exact Euclidean 1-NN (no distance cap) and the
  * lazily estimated normal of every hit.  Outputs [n,3], [n,3], [n] (any may be NULL). */

@@ -1035,6 +1035,8 @@ int icp_map_update_vertex_map(icp_ctx* ctx, const float rel_pose[16], const floa
 
 int64_t icp_map_size(const icp_ctx* ctx) { return ctx ? ctx->map_m : 0; }
 int icp_handoff_fallbacks(const icp_ctx* ctx) { return ctx ? ctx->handoff_fallbacks : 0; }
+int icp_lead_registrations(const icp_ctx* ctx) { return ctx ? ctx->lead_registrations : 0; }
+int icp_registering_contexts(int device) { return device >= 0 && device < 64 ? g_registering[device].load() : -1; }
 int icp_first_build_launches(const icp_ctx* ctx) { return ctx ? ctx->first_launches : 0; }
 int icp_map_num_clouds(const icp_ctx* ctx) { return ctx ? (int)ctx->cloud_sizes.size() : 0; }
 

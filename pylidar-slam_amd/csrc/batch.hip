@@ -313,6 +313,9 @@ int icp_batch_register_launch(icp_batch* b, const float* const* xyz, const int64
         if ((rc = register_begin(ctx, xyz[i], n[i], mem, target_mode, (init_poses && !from_last) ? init_poses + 16 * i : nullptr,
                                  from_last != 0, &packs[i])))
             return batch_fail(b, rc, ctx->error);
+        // (register_begin has answered for this member alone: the batch answers for all of them below, and counts then)
+        ctx->lead_registrations -= ctx->lead_latched ? 1 : 0;
+        ctx->lead_latched = false;
         if (!fused_path(ctx) || ctx->lazy_now)
             return batch_fail(b, ICP_ERR_INVALID_ARGUMENT, "batched registration: the fused iteration path with eagerly estimated "
                                                           "normals only (see icp_set_option: fuse_iteration, lazy_fused, eager_normals_limit)");
@@ -327,7 +330,10 @@ int icp_batch_register_launch(icp_batch* b, const float* const* xyz, const int64
         lead = lead && ctxs[i]->lead_solve && !ctxs[i]->handoff_disabled;
     }
     lead = lead && g_registering[d].load() <= counted;
-    for (int i = 0; i < count; ++i) ctxs[i]->lead_latched = lead;
+    for (int i = 0; i < count; ++i) {
+        ctxs[i]->lead_latched = lead;
+        ctxs[i]->lead_registrations += lead ? 1 : 0;
+    }
     // ---- the iterations: all of them (forced count), or a first chunk — as many as the slowest member ran last time plus one —
     // with a live stop threshold (icp_batch_register_end enqueues more while a member is still running; launches behind
     // every member's stop would be no-ops that still cost their slot on the stream: a hundred of them with the default

@@ -544,6 +544,7 @@ struct icp_ctx {
     bool handoff_disabled = false;     // ... and no lead launches either (the user's "lead_solve" is left as set; setting it again re-arms them)
     bool lead_latched = false;         // lead launches for the registration in progress: decided once, in register_begin
     int tail_capacity = -1;            // workgroups of the tail's shape the device holds at once (-1: not asked yet)
+    int lead_registrations = 0;        // registrations whose launches were latched onto lead launches (icp_lead_registrations)
     int handoff_fallbacks = 0;         // registrations finished on per-iteration launches behind a timed-out hand-off
     bool batch_hold = false;           // a batched registration of this context holds iterations back (batch.hip: icp_batch): individual entry points refuse
     bool counted_registering = false;  // this context is counted among the registering contexts of its device (api.hip)

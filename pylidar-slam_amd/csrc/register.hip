@@ -65,7 +65,10 @@ int icp_pmap_register(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int ta
         }
         if (poll > 0 && (it + 1) % poll == 0 && it + 1 < iters) {
             int done = 0;
-            if ((rc = poll_done(ctx, &done))) return rc;
+            if ((rc = poll_done(ctx, &done))) {
+                ctx->in_registration = false;  // (as every other error exit of the loop: the context is not left "in registration")
+                return rc;
+            }
             if (done) break;
         }
     }
@@ -128,6 +131,7 @@ int register_begin(icp_ctx* ctx, const float* xyz, int64_t n, int mem, int targe
     // registration between two chunks of this one flipped the answer — a chunk without a lead publishes no pose, the next
     // lead chunk then took a stale one from the mailbox)
     ctx->lead_latched = ctx->lead_solve && !ctx->handoff_disabled && !device_shared_with_another_registration(ctx);
+    ctx->lead_registrations += ctx->lead_latched ? 1 : 0;
     ctx->in_registration = true;
     ctx->iter_in_registration = 0;
     ctx->cache_fresh = false;
@@ -304,7 +308,10 @@ static int recover_handoff(icp_ctx* ctx, RegState& st, std::vector<char>& block)
         ctx->iter_in_registration = st.iter;
         ctx->cache_fresh = false;  // (a map update in between has rebuilt the grid: the first launch searches everything)
         ctx->searches_in_registration = 0;
-        if (!ctx->normals_ready && wants_eager_normals(ctx, ctx->tgt_n) && (rc = launch_normals_all(ctx))) return rc;
+        if (!ctx->normals_ready && wants_eager_normals(ctx, ctx->tgt_n) && (rc = launch_normals_all(ctx))) {
+            ctx->in_registration = false;  // (register_collect's RegisteringGuard then leaves the count)
+            return rc;
+        }
         rc = enqueue_iterations(ctx, false, st.iter, -1);
         ctx->in_registration = false;
         if (rc) return rc;
@@ -481,7 +488,11 @@ static int enqueue_iterations(icp_ctx* ctx, bool poll_allowed, int first, int co
         }
         if (poll > 0 && (it + 1) % poll == 0 && it + 1 < iters) {
             int done = 0;
-            if ((rc = poll_done(ctx, &done))) return rc;
+            if ((rc = poll_done(ctx, &done))) {
+                // (icp_register's RegisteringGuard leaves the count only for a context that is not "in registration")
+                ctx->in_registration = false;
+                return rc;
+            }
             if (done) break;
         }
     }

@@ -168,6 +168,8 @@ EXPORTED_SYMBOLS = {
     "icp_map_num_clouds": (_INT, [_P]),
     "icp_handoff_fallbacks": (_INT, [_P]),
     "icp_first_build_launches": (_INT, [_P]),
+    "icp_lead_registrations": (_INT, [_P]),
+    "icp_registering_contexts": (_INT, [_INT]),
     "icp_map_get": (_INT, [_P, _P, _INT]),
     "icp_nearest_neighbor_search": (_INT, [_P, _P, _I64, _INT, _P, _P, _P, _INT]),
     "icp_knn_query": (_INT, [_P, _P, _I64, _INT, C.c_int32, C.c_float, C.c_int32, _P, _P, _INT]),

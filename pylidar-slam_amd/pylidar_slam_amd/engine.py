@@ -142,6 +142,12 @@ def _frame_arrays(data, timestamps=None, vertex_map: bool = False, who: str = ""
     return (p if n else None), n, mem, FRAME_ROWS, (tp if n else None), (pts, ts)
 
 
+def registering_contexts(device: int = 0) -> int:
+    """Contexts of this process in a registration against the kd-tree style map, or holding an uncollected result of one, on
+    `device` right now (`icp_registering_contexts`; -1 outside 0..63)."""
+    return int(_lib.load_library().icp_registering_contexts(int(device)))
+
+
 def _pose16(m) -> "C.Array":
     a = np.ascontiguousarray(np.asarray(m, dtype=np.float32).reshape(4, 4))
     return (C.c_float * 16)(*a.reshape(-1).tolist())
@@ -504,6 +510,11 @@ class IcpContext:
     def handoff_fallbacks(self) -> int:
         """Registrations finished on per-iteration launches behind a timed-out hand-off (`icp_handoff_fallbacks`)."""
         return int(self._lib.icp_handoff_fallbacks(self._h))
+
+    def lead_registrations(self) -> int:
+        """Registrations of this context whose launches were latched onto lead launches when they began: no other context of
+        the process was registering on the device at that moment (`icp_lead_registrations`)."""
+        return int(self._lib.icp_lead_registrations(self._h))
 
     def first_build_launches(self) -> int:
         """Registrations whose first launch was the first-iteration build (`icp_first_build_launches`, option "first_build")."""

@@ -131,7 +131,7 @@ def _all(symbol, cell, control=NOTEETH, note="", **override):
 # ---- N/A: constructors, destructors, defaults, accessors of host fields
 for _s in ("icp_default_config", "icp_create", "icp_destroy", "icp_last_error", "icp_version", "icp_default_frame_config",
            "icp_default_pmap_frame_config", "icp_default_refine_params", "icp_map_size", "icp_map_num_clouds",
-           "icp_handoff_fallbacks", "icp_first_build_launches", "icp_pmap_num_maps", "icp_normal_equations_ptr",
+           "icp_handoff_fallbacks", "icp_first_build_launches", "icp_lead_registrations", "icp_registering_contexts", "icp_pmap_num_maps", "icp_normal_equations_ptr",
            "icp_batch_create", "icp_batch_destroy", "icp_batch_last_error", "icp_aggmap_create", "icp_aggmap_destroy",
            "icp_elevation_create", "icp_elevation_destroy", "icp_refine_create", "icp_refine_destroy"):
     _all(_s, NA)

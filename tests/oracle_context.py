@@ -28,6 +28,14 @@ class OracleContext:
     def use_torch_stream(self):
         pass
 
+    # the two diagnostics of the lead decision: the oracle has no launches and no neighbours
+    def lead_registrations(self):
+        return 0
+
+    @staticmethod
+    def registering_contexts(device=0):
+        return 0
+
     def set_cost(self, mode):
         self.cfg.alignment = "point_to_point" if "point_to_point" in mode else "point_to_plane"
 

@@ -12,6 +12,10 @@ iterations WERE held back when the call was made.
 Shapes: 16 x 512 scans, a fixed map of 10 000 points, max_num_alignments 20, geman_mcclure / 0.3, local_map_size 3: the
 smallest at which chunking exists (inflight_audit.kd_fixture; tests/test_inflight_audit.py asserts the hold-back on the CPU).
 
+Every scenario closes on `registering_contexts() == 0` once its contexts are closed (GpuRig.close): whatever the call under test
+did, refusals and error exits included, nothing of it stays in the device's count of registering contexts
+(tests/neighbour_audit.py holds that count call by call).
+
 THE OVERLAPPED STATE is one fixed sequence, run once: a pass shows no race on that run and proves no absence of one.
 """
 import ctypes as C
@@ -522,6 +526,9 @@ class GpuRig:
         for c in self.members + self.extras:
             c.close()
         self.keep.clear()
+        # (whatever the scenario did, error exits included: no context of it is left in the device's count of registering contexts)
+        from pylidar_slam_amd.engine import registering_contexts
+        assert registering_contexts(0) == 0, f"{self.state}: the count of registering contexts is left at {registering_contexts(0)}"
 
 
 # ---- the cells: every row with a recipe in the kd-tree states and the key frame; the frame that is no key frame and the projective
